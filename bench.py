@@ -13,14 +13,20 @@ Multi-GPU (torchrun, one rank per GPU, RCCL): dates are independent, so each ran
 its own contiguous block of 4749 dates of a longer panel (weak scaling); the only
 collective is the all-gather of the weight panels.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with a `roofline` object
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times ``--steps`` steps and
+prints the headline fields (`metric`, `value`, `unit`, `ms_per_step`, ...) with the stage
+times the HIP events of the timed steps give; ``--dump-outputs DIR`` also writes the last
+timed step's weights, status, iterations and objectives as ``DIR/<name>.npy``.  Every other
+leg runs only with ``--full``, which adds to the line: the KKT certificate of the last step,
+the solver statistics, the stage rates, a `roofline` object
 for the dominant kernel (K3 ADMM, `k_admm_gcap` on the group-capacitance window path; HBM
 roofline; algorithmic bytes per date-iteration = (2 x 8 U n union-row passes + 8 k(k+1)/2
 for the group's M_U^-1) / dates per group + 12 x 8 n of per-date ADMM state, timed with HIP
 events on the launch stream), the measured HBM fraction from the committed
 rocprofv3 PMC summary of the same code (``frac_hbm_measured``: PMC bytes per date-iteration
 x date-iterations / kernel time / peak), and a `cpu_baseline` object (the reference
-per-date path restated in numpy, oracle/cpu_baseline.py, on a bounded sample of dates).
+per-date path restated in numpy, oracle/cpu_baseline.py, on a bounded sample of dates),
+the simulate / LAD rows (config 3) and the end-to-end ``Backtest.run`` line.
 """
 from __future__ import annotations
 
@@ -133,8 +139,18 @@ def parse():
                          "config5: 64 dates in total")
     ap.add_argument("--path", choices=["auto", "dense", "lowrank"], default="auto",
                     help="dense K^-1 (K2 n^3 + K3 n^2 stream) or Woodbury low-rank (T + mg < n)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the end-to-end Backtest.run line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg and add it to the result line: the "
+                         "CPU baseline, the KKT certificate of the last step, the roofline and stage rates, "
+                         "the solver statistics, the simulate / LAD rows and the end-to-end Backtest.run "
+                         "(a plain run sets up, warms up, times the steps and prints the headline fields)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy "
+                         "(float64): weights (the gathered panel on rank 0's host, dates x assets), and "
+                         "rank 0's status, iters and obj per date; outputs above 64 MB in all are cut to a "
+                         "fixed seeded sample of dates, whose indices are DIR/dates.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-dropin", action="store_true", help="--full without the end-to-end Backtest.run line")
     ap.add_argument("--no-group", action="store_true",
                     help="low-rank ADMM one workgroup per date instead of per group of sliding windows")
     ap.add_argument("--no-slide", action="store_true",
@@ -243,8 +259,35 @@ def run_ranks(envs, argv, script=None) -> int:
     return rc
 
 
+DUMP_BYTES = 60 * 10 ** 6   # --dump-outputs writes at most this much array data (files stay below 64 MB in all)
+
+
+def dump_sample(n_dates: int, row_bytes: int, budget: int = DUMP_BYTES, seed: int = 20240314):
+    """The dates --dump-outputs writes: every date if ``n_dates`` rows of ``row_bytes`` fit in
+    ``budget``, otherwise a sorted sample of as many as fit, fixed by ``seed``."""
+    keep = budget // row_bytes
+    if n_dates <= keep:
+        return np.arange(n_dates)
+    return np.sort(np.random.default_rng(seed).choice(n_dates, size=keep, replace=False))
+
+
+def dump_outputs(path: str, weights: np.ndarray, res) -> None:
+    """Write the last timed step's results (rank 0): ``weights`` is the host panel the step's
+    gather filled (every rank's dates), ``res`` this rank's BatchResult."""
+    os.makedirs(path, exist_ok=True)
+    # per date: one row of weights + dates index, status, iters, obj
+    sel = dump_sample(weights.shape[0], 8 * (weights.shape[1] + 4))
+    local = sel[sel < res.status.shape[0]]
+    arrays = {"dates": sel, "weights": weights[sel], "status": res.status.cpu().numpy()[local],
+              "iters": res.iters.cpu().numpy()[local], "obj": res.obj.cpu().numpy()[local]}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     args = parse()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
     plan = launch_plan(args.gpus, os.environ)
     if plan is not None:
         sys.exit(run_ranks(plan, sys.argv[1:]))
@@ -264,7 +307,7 @@ def main():
     # CPU baseline first, in a child process, before this process touches the GPU (its
     # process pool forks; bench.py itself never forks after HIP initialisation)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import subprocess
         # bounded samples: the per-QP reference cost grows with n^3 (nearestPD's SVD + eigvals:
         # ~0.3 s at n = 494, ~2 s at 1000, ~40 s at 3000, minutes at 5000 on one core), so the
@@ -380,6 +423,41 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:   # the last timed step's host panel (its copy has completed)
+        dump_outputs(args.dump_outputs, w_host[(nstep[0] - 1) % nbuf].numpy(), res)
+    # ---- per-kernel timing (HIP events on the launch stream) ------------------------------
+    tk = {}
+    cnt = {}
+    for name, a, b in events:
+        tk[name] = tk.get(name, 0.0) + a.elapsed_time(b) * 1e-3
+        cnt[name] = cnt.get(name, 0) + 1
+    qps = D_all * args.steps / dt
+    head = {
+        "metric": "QPs solved/sec (rebalance dates) at N=1000 assets, 1-8 GPU; x vs host CPU",
+        "value": qps,
+        "unit": "QPs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if args.strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": ("synthetic usa-shaped panel (494 assets loading on the real SPTR returns, seed 20240101; "
+                 "usa_returns absent) on the real SPTR calendar" if wname in ("config1", "config2") else
+                 "synthetic (factor-model panel, seed 20240314; usa_returns absent)"),
+        "config": {"workload": WORKLOAD_TEXT[wname], "n_assets": n, "window": T,
+                   "dates_per_gpu": D, "global_batch": D_all,
+                   "parallelism": (f"dates-sharded x{world} (every lambda of a date on its rank)"
+                                   if wname == "config5" else f"dates-sharded x{world}")},
+    }
+    if not args.full:   # a plain run ends here: the headline fields and the stage times of the timed steps
+        if rank == 0:
+            print(json.dumps(dict(head, stages_s_per_step={k: v / args.steps for k, v in tk.items()})), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
 
     # ---- accuracy of every solution of the last step (outside the timed region): primal
     # violation and relative stationarity recomputed from the panel rows with torch -------
@@ -392,12 +470,6 @@ def main():
         st_all = torch.bincount((res.status.long() + 8).clamp(0, 15), minlength=16).to(red_dev)
         dist.all_reduce(st_all)
         cert["status_counts"] = {str(i - 8): int(v) for i, v in enumerate(st_all.tolist()) if v}
-    # ---- per-kernel timing (HIP events on the launch stream) ------------------------------
-    tk = {}
-    cnt = {}
-    for name, a, b in events:
-        tk[name] = tk.get(name, 0.0) + a.elapsed_time(b) * 1e-3
-        cnt[name] = cnt.get(name, 0) + 1
     iters = res.iters.to(torch.int64)
     total_iters = int(iters.sum().item()) * args.steps   # identical work every step
     status = res.status.cpu().numpy()
@@ -499,26 +571,8 @@ def main():
     frac_hbm_measured = (traffic * (total_iters // args.steps) / (tk["admm"] / args.steps) / 1e9 / HBM_PEAK_GBS
                          if traffic is not None else None)
 
-    qps = D_all * args.steps / dt
     out = {
-        "metric": "QPs solved/sec (rebalance dates) at N=1000 assets, 1-8 GPU; x vs host CPU",
-        "value": qps,
-        "unit": "QPs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong" if args.strong else "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": ("synthetic usa-shaped panel (494 assets loading on the real SPTR returns, seed 20240101; "
-                 "usa_returns absent) on the real SPTR calendar" if wname in ("config1", "config2") else
-                 "synthetic (factor-model panel, seed 20240314; usa_returns absent)"),
-        "config": {"workload": WORKLOAD_TEXT[wname], "n_assets": n, "window": T,
-                   "dates_per_gpu": D, "global_batch": D_all,
-                   "parallelism": (f"dates-sharded x{world} (every lambda of a date on its rank)"
-                                   if wname == "config5" else f"dates-sharded x{world}")},
+        **head,
         "roofline": {"bound": "hbm", "kernel": kern + (" + k_sw_mid (K3, risk-aversion sweep)" if kern == "k_sw_pass"
                                                        else " (K3, grouped low-rank)" if grouped else " (K3)"),
                      "achieved": admm_gbs,

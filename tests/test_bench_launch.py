@@ -45,6 +45,41 @@ def test_run_ranks_stops_the_others_when_a_rank_fails(tmp_path):
     assert rc == 3 and time.time() - t0 < 60
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_sample_is_fixed_and_within_the_budget():
+    assert bench.dump_sample(4749, 8 * 1004).tolist() == list(range(4749))     # config 3: every date fits
+    s = bench.dump_sample(9749, 8 * 3004)                                      # config 4: a sample
+    assert len(s) == bench.DUMP_BYTES // (8 * 3004) and len(s) * 8 * 3004 + 5 * 128 <= 64 * 10 ** 6
+    assert len(set(s.tolist())) == len(s) and s.min() >= 0 and s.max() < 9749 and (s[1:] > s[:-1]).all()
+    assert s.tolist() == bench.dump_sample(9749, 8 * 3004).tolist()            # the same dates every run
+
+
+def test_dump_outputs_writes_float64_arrays_of_the_last_step(tmp_path):
+    import types
+
+    import numpy as np
+    import torch
+    D, n = 5, 3
+    w = np.arange(D * n, dtype=np.float64).reshape(D, n)
+    res = types.SimpleNamespace(status=torch.ones(D, dtype=torch.int32),
+                                iters=torch.arange(D, dtype=torch.int32), obj=torch.arange(D, dtype=torch.float64) / 7)
+    out = tmp_path / "dump" / "run"
+    bench.dump_outputs(str(out), w, res)
+    assert sorted(os.listdir(out)) == ["dates.npy", "iters.npy", "obj.npy", "status.npy", "weights.npy"]
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["weights"], w) and np.array_equal(got["dates"], np.arange(D))
+    assert np.array_equal(got["iters"], np.arange(D)) and np.array_equal(got["obj"], np.arange(D) / 7)
+
+
 def test_pmc_summary_selection_takes_the_newest_matching_profile(tmp_path):
     """bench.py's roofline traffic comes from the newest PMC summary of the SAME code: the
     algorithmic bytes AND the date-iterations per step must match; uppercase run letters

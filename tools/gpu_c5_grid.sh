@@ -3,12 +3,13 @@
 set -o pipefail
 export PYTHONUNBUFFERED=1
 T=${1:-rXX}
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 CFGS=("0.5 7" "1.0 7" "0.25 7" "0.5 5" "2.0 7")
 [ -n "$GRID" ] && IFS=, read -ra CFGS <<< "$GRID"   # e.g. GRID="0.6 7,0.7 7"
 for cfg in "${CFGS[@]}"; do
   set -- $cfg
-  timeout -k 10 300 python -u bench.py --workload config5 --steps 4 --no-cpu-baseline --set eps_grouped=$1 --set min_iter_grouped=$2 > gpurun_out/${T}_c5_eps$1_min$2.log 2>&1 || { echo "bench $cfg failed"; exit 5; }
-  python - gpurun_out/${T}_c5_eps$1_min$2.log "$cfg" <<'PY'
+  timeout -k 10 300 python -u bench.py --full --workload config5 --steps 4 --no-cpu-baseline --set eps_grouped=$1 --set min_iter_grouped=$2 > $OUT/${T}_c5_eps$1_min$2.log 2>&1 || { echo "bench $cfg failed"; exit 5; }
+  python - $OUT/${T}_c5_eps$1_min$2.log "$cfg" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 s = d["solver"]

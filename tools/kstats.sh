@@ -1,13 +1,13 @@
 # rocprofv3 kernel stats of one short bench run: bash tools/kstats.sh <tag> [bench args...]
-# -> gpurun_out/<tag>_kstats.csv, top kernels printed per step (steps = k_admm_gcap calls)
+# -> $OUT/<tag>_kstats.csv (OUT: bench_out), top kernels printed per step (steps = k_admm_gcap calls)
 set -o pipefail
 TAG=$1; shift
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 rm -rf /tmp/kst_$TAG
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d /tmp/kst_$TAG -o run -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-dropin "$@" > gpurun_out/${TAG}_kstats_bench.log 2>&1 || exit 1
-cp /tmp/kst_$TAG/run_kernel_stats.csv gpurun_out/${TAG}_kstats.csv
-python3 - gpurun_out/${TAG}_kstats.csv <<'PY'
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d /tmp/kst_$TAG -o run -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-dropin "$@" > $OUT/${TAG}_kstats_bench.log 2>&1 || exit 1
+cp /tmp/kst_$TAG/run_kernel_stats.csv $OUT/${TAG}_kstats.csv
+python3 - $OUT/${TAG}_kstats.csv <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 steps = max(1, sum(int(r['Calls']) for r in rows if r['Name'].startswith('k_admm_gcap')))

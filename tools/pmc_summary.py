@@ -41,7 +41,7 @@ def per_kernel(path, counter, first=None):
 
 def main():
     rnd = sys.argv[1] if len(sys.argv) > 1 else "r01"
-    src = os.path.join(ROOT, "gpurun_out", f"prof_{rnd}")
+    src = os.path.join(ROOT, os.environ.get("OUT", "bench_out"), f"prof_{rnd}")   # profile_round.sh's $OUT
     dst = os.path.join(ROOT, "profiles")
     os.makedirs(dst, exist_ok=True)
     shutil.copy(os.path.join(src, "trace", "run_kernel_stats.csv"),
@@ -62,7 +62,7 @@ def main():
         else:
             stats[k] = r
     out = {"round": rnd, "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of "
-                                   "`bench.py --steps 1 --warmup 0` (one step = the whole backtest)",
+                                   "`bench.py --full --steps 1 --warmup 0` (one step = the whole backtest)",
            "admm_iterations_per_step": iters, "kernels": {}}
     for k in sorted(fetch, key=lambda k: -fetch[k]):
         rd = 2.0 * fetch[k] * 1024.0

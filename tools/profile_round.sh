@@ -1,5 +1,5 @@
 #!/bin/bash
-# Profile collection for one round (run on the GPU box via gpurun).  Writes under gpurun_out/prof_$1.
+# Profile collection for one round (run on the GPU box).  Writes under $OUT/prof_$1 (OUT: bench_out).
 #  1. kernel trace + stats of a short bench run
 #  2. separate PMC passes (never combined with tracing): FETCH_SIZE, WRITE_SIZE, then the
 #     MFMA-busy pass (SQ_VALU_MFMA_BUSY_CYCLES + GRBM_GUI_ACTIVE)
@@ -9,16 +9,16 @@
 set -o pipefail
 R=${1:-r01}
 W=${2:-config3}
-OUT=gpurun_out/prof_$R
+OUT=${OUT:-bench_out}/prof_$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-B="bench.py --workload $W --no-cpu-baseline --no-dropin"
+B="bench.py --full --workload $W --no-cpu-baseline --no-dropin"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/trace -o run -- python3 $B --steps 2 --warmup 1 > $OUT/trace_bench.log 2>&1 || { echo "trace failed"; exit 1; }
 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -T --output-format csv -d $OUT/pmc_fetch -o run -- python3 $B --steps 1 --warmup 0 > $OUT/pmc_fetch.log 2>&1 || { echo "pmc fetch failed"; exit 1; }
 timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE -T --output-format csv -d $OUT/pmc_write -o run -- python3 $B --steps 1 --warmup 0 > $OUT/pmc_write.log 2>&1 || { echo "pmc write failed"; exit 1; }
 timeout -s KILL 240 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE -T --output-format csv -d $OUT/pmc_mfma -o run -- python3 $B --steps 1 --warmup 0 > $OUT/pmc_mfma.log 2>&1 || { echo "pmc mfma failed"; exit 1; }
 if [ -z "$NOFULL" ]; then
-  timeout -k 10 900 python3 bench.py --workload $W --steps 3 --warmup 1 > $OUT/bench_full.log 2>&1 || { echo "bench failed"; exit 1; }
+  timeout -k 10 900 python3 bench.py --full --workload $W --steps 3 --warmup 1 > $OUT/bench_full.log 2>&1 || { echo "bench failed"; exit 1; }
   tail -1 $OUT/bench_full.log
 fi
 find $OUT -name "*.csv" | head -20
