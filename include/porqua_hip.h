@@ -250,7 +250,8 @@ int pq_factor_large(const pq_problem* pb, pq_state* st, const int32_t* idx, int3
 
 /* K3: up to `iters_this_call` OSQP-style ADMM iterations per problem idx[] (stops a
  * problem at convergence, at settings.max_iter, or when adaptive rho requests a
- * refactorisation: status PQ_NEED_REFACTOR and rho[] already updated).
+ * refactorisation: status PQ_NEED_REFACTOR and rho[] already updated; none is requested
+ * at iteration max_iter itself, where the status is PQ_MAX_ITER -- all K3 entry points).
  * Replaces qpsolvers.solve_problem (src/qp_problems.py:211-214).                        */
 int pq_admm_batched(const pq_problem* pb, pq_state* st, const int32_t* idx, int32_t nidx,
                     const pq_settings* s, int32_t iters_this_call, void* stream);
@@ -313,9 +314,13 @@ int pq_admm_lr_grouped(const pq_lowrank* lr, const pq_problem* pb, pq_state* st,
  * pass 2, the updates, the next rhs and its pass-1 partial (the window chunk read once for
  * all problems of the group), then one per problem for the M_b^-1 symv -- instead of one
  * workgroup per group.  Same iterates as the fused pq_admm_lr_grouped up to summation
- * order; one flag read between blocks of iterations.  Needs tmax <= 256, k_ld <= 256, shared
+ * order; one flag read between blocks of iterations.  Needs tmax <= 256, k_ld <= 256 and a
+ * multiple of 64 (checked: M_b^-1 is read in 64-column blocks), shared
  * general rows mg <= 4 with pc / cc (mg > 0), shared box rows, uniform ADMM diagonal, and
- * scratch_doubles >= pq_sweep_scratch_doubles(n, batch, ngroups).  q_shared != 0: the problems
+ * scratch_doubles >= pq_sweep_scratch_doubles(n, batch, ngroups).  Precondition, NOT checked
+ * (gdates is device memory): gdates[g+1] - gdates[g] <= 64 for every group -- the problems of
+ * a group are the 64 MFMA columns of one workgroup and index 64-wide scratch slabs, so a
+ * larger group reads and writes out of bounds.  q_shared != 0: the problems
  * of a group share q too (q_b = -mu_d for every risk aversion), read from the group's first
  * problem.  Replaces
  * qpsolvers.solve_problem (src/qp_problems.py:211-214) for the sweep of

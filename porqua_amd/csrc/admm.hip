@@ -513,7 +513,9 @@ __global__ __launch_bounds__(AT) void k_admm(pq_problem pb, pq_state st, const i
       status = PQ_SOLVED;
       break;
     }
-    if (s.adapt_interval > 0 && it % s.adapt_interval == 0) {
+    // (not at max_iter itself: the run ends there, and a rho request would cost a
+    // refactorisation that no iteration uses)
+    if (s.adapt_interval > 0 && it % s.adapt_interval == 0 && it < s.max_iter) {
       const double rp = mv[0] / (fmax(mv[1], mv[2]) + 1e-30);
       const double rd = mv[3] / (fmax(mv[4], fmax(mv[5], mv[6])) + 1e-30);
       double rn = rho * sqrt(rp / (rd + 1e-30));

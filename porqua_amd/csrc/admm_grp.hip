@@ -658,7 +658,9 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
       double rnew = rho;
       if (it >= s.min_iter && mv[0] <= eps_p && mv[3] <= eps_d) {
         stat = PQ_SOLVED;
-      } else if (s.adapt_interval > 0 && it % s.adapt_interval == 0) {
+      } else if (s.adapt_interval > 0 && it % s.adapt_interval == 0 && it < s.max_iter) {
+        // (not at max_iter itself: a date left NEED_REFACTOR there was resumed after the
+        // refactorisation for one iteration beyond max_iter)
         const double rp = mv[0] / (fmax(mv[1], mv[2]) + 1e-30);
         const double rd = mv[3] / (fmax(mv[4], fmax(mv[5], mv[6])) + 1e-30);
         double rn = rho * sqrt(rp / (rd + 1e-30));

@@ -628,7 +628,9 @@ __global__ __launch_bounds__(SW_MT) void k_sw_mid(pq_lowrank lr, pq_problem pb, 
       double rnew = rho;
       if (it >= s.min_iter && mv0 <= eps_p && mv3 <= eps_d) {
         stat = PQ_SOLVED;
-      } else if (s.adapt_interval > 0 && it % s.adapt_interval == 0) {
+      } else if (s.adapt_interval > 0 && it % s.adapt_interval == 0 && it < s.max_iter) {
+        // (not at max_iter itself: a problem left NEED_REFACTOR there was resumed after the
+        // refactorisation for one iteration beyond max_iter)
         const double rp = mv0 / (fmax(mv1, mv2) + 1e-30);
         const double rd = mv3 / (fmax(mv4, fmax(mv5, mv6)) + 1e-30);
         double rn = rho * sqrt(rp / (rd + 1e-30));
@@ -852,7 +854,9 @@ extern "C" int pq_admm_lr_sweep(const pq_lowrank* lr, const pq_problem* pb, pq_s
                    (int64_t)pb->batch * pb->q_stride < (int64_t)1 << 31,
                "pq_admm_lr_sweep: state arrays beyond 32-bit element offsets");
   const int k = lr->tmax + pb->mg;
-  PQ_CHECK_ARG(k <= k_ld && k_ld <= pq::SW_K, "pq_admm_lr_sweep: need k <= k_ld <= %d (k=%d)", pq::SW_K, k);
+  // (k_sw_mid reads M^-1 in 64-column blocks, up to column 64 ceil(k / 64) - 1 of a row)
+  PQ_CHECK_ARG(k_ld % 64 == 0 && k <= k_ld && k_ld <= pq::SW_K,
+               "pq_admm_lr_sweep: need k <= k_ld <= %d, k_ld a multiple of 64 (k=%d k_ld=%d)", pq::SW_K, k, k_ld);
   PQ_CHECK_ARG(scratch_doubles >= pq_sweep_scratch_doubles(pb->n, pb->batch, ngroups),
                "pq_admm_lr_sweep: scratch too small");
   if (ngroups <= 0 || iters_this_call <= 0) return 0;

@@ -984,6 +984,7 @@ def solve_lowrank(qb: QPBatch, lr: LowRank, settings: Settings | None = None,
     lib = _lib.load()
     s = (settings or Settings()).to_c()
     ws = ws or Workspace(qb, dense=False)
+    ws.sweep_admm = None   # set below when pq_admm_lr_sweep runs (a reused workspace must not keep it)
     B, dev = qb.batch, qb.device
     ldk = ws.ldk
     k = lr.tmax + qb.mg
@@ -1333,7 +1334,7 @@ def window_rows(dates: np.ndarray, rebdates, width: int):
     idx = first.astype(np.int32)[:, None] + j
     if len(wpos) != len(dates):
         idx = wpos[np.minimum(idx, len(wpos) - 1)]
-    if int(tlen.min()) == tmax:   # every window full (the usual backtest): nothing to mask
+    if B and int(tlen.min()) == tmax:   # every window full (the usual backtest): nothing to mask
         return idx.astype(np.int32, copy=False), tlen
     rows = idx * (j < tlen[:, None])
     return rows.astype(np.int32, copy=False), tlen
@@ -1417,7 +1418,12 @@ class SweepPlan:
     """Problem groups for pq_admm_lr_sweep (admm_sweep.hip): runs of up to 64 consecutive
     problems that share one window and its centring (the risk-aversion row of a rebalance
     date, porqua_amd.sweep), with the kernel's scratch (per-problem records, per-chunk
-    partials, the pass-2 operand).  ``q_shared``: the problems of a group share q as well."""
+    partials, the pass-2 operand).  ``q_shared``: the problems of a group share q as well.
+
+    Precondition of the kernel (not checked on the device): gdates[g + 1] - gdates[g] <= 64
+    for every group -- a group's problems are the 64 MFMA columns of one workgroup.  The plan
+    built here never emits a larger group (``counts`` above 64 are cut into runs of 64 and a
+    remainder); a hand-made gdates must keep to it."""
 
     GMAX = 64
 

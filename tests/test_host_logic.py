@@ -480,3 +480,29 @@ def test_sweep_plan_groups_and_applicability():
     assert not sp.applicable(qs, LR(), 256)   # per-problem rows / boxes
     need = _lib.load().pq_sweep_scratch_doubles(5000, 4096, 64)
     assert need == 4096 * 80 + 64 * 20 * 64 * (256 + 16) + 64 * 256 * 64 + 64
+
+
+@pytest.mark.parametrize("counts", [[1], [64], [65], [128], [129], [70, 3, 64]])
+def test_sweep_plan_never_emits_a_group_beyond_64(counts):
+    """pq_admm_lr_sweep's unchecked precondition gdates[g + 1] - gdates[g] <= 64 (a group's
+    problems are the 64 MFMA columns of one workgroup): the plan cuts longer rows, covers
+    every problem once, in order, and never joins two rows."""
+    sp = engine.SweepPlan(counts, "cpu")
+    gd = np.asarray(sp.gdates.tolist())
+    sizes = np.diff(gd)
+    assert gd[0] == 0 and gd[-1] == sum(counts) and sp.ngroups == len(sizes)
+    assert sizes.min() >= 1 and sizes.max() <= engine.SweepPlan.GMAX == 64
+    assert sp.ngroups == sum(-(-c // 64) for c in counts)
+    assert set(np.cumsum(counts).tolist()) <= set(gd.tolist())   # no group straddles two rows
+
+
+def test_window_rows_without_rebalance_dates():
+    """No rebalance dates on a non-empty calendar: empty plans (the full-window fast path
+    once took the minimum of an empty tlen)."""
+    dates, _, _, _ = factor_panel(40, 4)
+    for reb in ([], np.array([], dtype="datetime64[D]")):
+        rows, tlen = engine.window_rows(dates, reb, 10)
+        assert rows.shape == (0, 1) and rows.dtype == np.int32
+        assert tlen.shape == (0,) and tlen.dtype == np.int32
+    rows, tlen = engine.window_rows(dates, dates[[9, 20]], 10)   # (the fast path itself still runs)
+    assert tlen.tolist() == [10, 10] and np.array_equal(rows[1], np.arange(11, 21))
