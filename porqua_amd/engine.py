@@ -168,10 +168,9 @@ class Settings:
     # is within this fraction of the problem scale of the wrong sign (0: off; see pq_settings)
     polish_release_rel: float = 0.0
 
-    def to_c(self) -> _lib.PQSettings:
-        names = {f[0] for f in _lib.PQSettings._fields_}
-        return _lib.PQSettings(**{f.name: getattr(self, f.name) for f in dataclasses.fields(self)
-                                  if f.name in names})
+    def to_c(self, **override) -> _lib.PQSettings:
+        """The C settings struct, with ``override`` replacing fields (derived settings of one solve)."""
+        return _lib.PQSettings(**{**{k: getattr(self, k) for k in _C_SETTINGS}, **override})
 
     @classmethod
     def from_params(cls, params) -> "Settings":
@@ -185,6 +184,9 @@ class Settings:
                             v = v.strip().lower() not in ("0", "false", "no", "off", "")
                         setattr(s, f.name, typ(v))
         return s
+
+
+_C_SETTINGS = tuple(c[0] for c in _lib.PQSettings._fields_ if c[0] in Settings.__dataclass_fields__)   # (not host-side)
 
 
 # ----------------------------------------------------------------------------------------
@@ -356,30 +358,30 @@ class Workspace:
         self.out = torch.zeros((B, _lib.PQ_OUT_FIELDS), dtype=F64, device=dev)
         self.work_stride = _lib.work_doubles(ld, qb.mg_pad)
         self.work = torch.zeros((B, self.work_stride), dtype=F64, device=dev)
+        # set by every solve_lowrank for its callers: the group capacitance's plan and the SweepPlan the
+        # ADMM ran on, the band Gram's (rows, width), the dates the grouped polish handed back
+        self.gcap_groups = self.sweep_admm = self.band_shape = self.pg_fallback = None
+        # built on first use and kept (captured graphs point to them): the grouped polish's record and
+        # pass scratch, the sync-free flag, the GroupCap of the ADMM and of the wide polish rounds
+        self._pg_rec = self._pg_pass = self._sf_flag = self._gcap = self._pgw = None
 
     def pg_record(self):
         """Per-problem record of the grouped polish pipeline (PQ_PG_RECORD doubles each)."""
-        if getattr(self, "_pg_rec", None) is None:
+        if self._pg_rec is None:
             self._pg_rec = torch.zeros((self.B, _lib.PQ_PG_RECORD), dtype=F64, device=self.device)
         return self._pg_rec
 
     def lr_buffers(self, k_ld: int):
         """Capacitance matrices M, their inverses and factor scratch (low-rank path)."""
         if self._lr is None or self._lr["k_ld"] != k_ld:
-            B, dev = self.B, self.device
-            self._lr = {"k_ld": k_ld,
-                        "M": torch.empty((B, k_ld, k_ld), dtype=F64, device=dev),
-                        "Minv": torch.empty((B, k_ld, k_ld), dtype=F64, device=dev),
-                        "Dt": torch.empty((B, k_ld // 64, 64, 64), dtype=F64, device=dev),
-                        "iters": torch.zeros(B, dtype=torch.int32, device=dev),
-                        "status": torch.zeros(B, dtype=torch.int32, device=dev),
-                        "info": torch.zeros(B, dtype=torch.int32, device=dev)}
+            self._lr = dict(_matrix_stack(self.B, k_ld, self.device), k_ld=k_ld)
         return self._lr
 
-    def c_struct(self) -> _lib.PQState:
+    def c_struct(self, K=None, Dt=None) -> _lib.PQState:
+        """The state struct; ``K`` / ``Dt``: another matrix stack and factor scratch in place of the workspace's."""
+        K, Dt = self.K if K is None else K, self.Dt if Dt is None else Dt
         return _lib.PQState(
-            K=self.K.data_ptr(), K_stride=self.K.stride(0),
-            Dt=self.Dt.data_ptr(), Dt_stride=self.Dt.stride(0),
+            K=K.data_ptr(), K_stride=K.stride(0), Dt=Dt.data_ptr(), Dt_stride=Dt.stride(0),
             x=self.x.data_ptr(), Px=self.Px.data_ptr(),
             z=self.z.data_ptr(), y=self.y.data_ptr(),
             m_ld=self.m_ld, mg_pad=self.mg_pad,
@@ -490,14 +492,15 @@ def solve(qb: QPBatch, settings: Settings | None = None, ws: Workspace | None = 
     appended for every launch (recorded on the launch stream)."""
     tl = _Timeline(events)
     lib = _lib.load()
-    s = (settings or Settings()).to_c()
+    settings = settings or Settings()
+    s = settings.to_c()
     ws = ws or Workspace(qb)
     pb = qb.c_struct()
     st = ws.c_struct()
     strm = _stream()
     P_, S_, SS = ctypes.byref(pb), ctypes.byref(st), ctypes.byref(s)
     _lib.check(lib.pq_init_state(P_, S_, None, 0, SS, strm), "pq_init_state")
-    _rho_floor_q(qb, ws, settings or Settings())
+    _rho_floor_q(qb, ws, settings)
     _lib.check(tl("factor", lambda: lib.pq_factor_batched(P_, S_, None, 0, SS, 1, strm)),
                "pq_factor_batched")
     cnt = {"refactors": 0, "launches": 0}
@@ -521,12 +524,12 @@ def solve(qb: QPBatch, settings: Settings | None = None, ws: Workspace | None = 
     if s.polish:
         _lib.check(tl("polish", lambda: lib.pq_polish_batched(P_, S_, None, 0, SS, strm)),
                    "pq_polish_batched")
-        rp = _repolish_set(ws, settings or Settings())
+        rp = _repolish_set(ws, settings)
         if rp is not None:      # polish rejected: polish again with more refinement steps
             pidx, pn, s3 = rp
             _lib.check(tl("polish", lambda: lib.pq_polish_batched(P_, S_, _ptr(pidx), pn, ctypes.byref(s3), strm)),
                        "pq_polish_batched (refine)")
-        retry = _retry_set(ws, settings or Settings())
+        retry = _retry_set(ws, settings)
         if retry is not None:   # polish rejected: resume ADMM to eps_retry, polish again
             idx, nidx, s2 = retry
             # the polish used K as scratch: restore K^-1 (current rho) before resuming
@@ -535,11 +538,13 @@ def solve(qb: QPBatch, settings: Settings | None = None, ws: Workspace | None = 
             admm_rounds(idx, nidx, ctypes.byref(s2))
             _lib.check(tl("polish", lambda: lib.pq_polish_batched(P_, S_, _ptr(idx), nidx, SS, strm)),
                        "pq_polish_batched (retry)")
-    refactors, launches = cnt["refactors"], cnt["launches"]
+    return _batch_result(qb, ws, refactors=cnt["refactors"], admm_launches=cnt["launches"])
+
+
+def _batch_result(qb: "QPBatch", ws: "Workspace", **counts) -> BatchResult:
     n, mg = qb.n, qb.mg
     return BatchResult(x=ws.x[:, :n], y=ws.y[:, :mg], z_box=ws.y[:, ws.mg_pad:ws.mg_pad + n],
-                       status=ws.status, iters=ws.iters, out=ws.out, refactors=refactors,
-                       admm_launches=launches)
+                       status=ws.status, iters=ws.iters, out=ws.out, **counts)
 
 
 def _rho_floor_q(qb: "QPBatch", ws: "Workspace", settings: Settings):
@@ -561,9 +566,7 @@ def _repolish_set(ws: "Workspace", settings: Settings):
     if m == 0:
         return None
     ws.status[bad.long()] = _lib.PQ_SOLVED
-    s3 = settings.to_c()
-    s3.refine_iters = settings.refine_retry
-    return bad.contiguous(), m, s3
+    return bad.contiguous(), m, settings.to_c(refine_iters=settings.refine_retry)
 
 
 def _retry_set(ws: "Workspace", settings: Settings):
@@ -574,9 +577,7 @@ def _retry_set(ws: "Workspace", settings: Settings):
     if m == 0 or settings.eps_retry <= 0 or settings.eps_retry >= min(settings.eps_abs, settings.eps_rel):
         return None
     ws.status[bad.long()] = _lib.PQ_UNSOLVED
-    s2 = settings.to_c()
-    s2.eps_abs = s2.eps_rel = settings.eps_retry
-    return bad.contiguous(), m, s2
+    return bad.contiguous(), m, settings.to_c(eps_abs=settings.eps_retry, eps_rel=settings.eps_retry)
 
 
 class LowRank:
@@ -589,6 +590,7 @@ class LowRank:
         self.panel, self.rows, self.tlen, self.mu, self.w_scale = panel, rows, tlen, mu, w_scale
         self.tmax = int(rows.shape[1])
         self.dg = dg if dg is not None else panel.window_sumsq(rows, tlen, mu)
+        self._span = None
 
     def refresh(self):
         self.panel.window_sumsq(self.rows, self.tlen, self.mu, out=self.dg)
@@ -596,7 +598,7 @@ class LowRank:
 
     def span(self):
         """(r0, nrows, W): the panel rows the windows touch and the widest window span."""
-        if getattr(self, "_span", None) is None:
+        if self._span is None:
             t = self.tlen.to(torch.int64)
             first = self.rows[:, 0].to(torch.int64)
             last = self.rows.gather(1, (t - 1).clamp(min=0)[:, None]).flatten().to(torch.int64)
@@ -767,11 +769,16 @@ def _uniform_box(qb: QPBatch) -> bool:
     return _cached(qb, "_c_ubox", _tkey(qb.lb, qb.ub), check, keep=(qb.lb, qb.ub))
 
 
+def _band_applies(qb: QPBatch, lr: LowRank) -> bool:
+    """Shared constraints, tmax <= 1024 and one ADMM rho for every box row (a cached device check)."""
+    return qb.shared and lr.tmax <= 1024 and _uniform_box(qb)
+
+
 def _band_setup(qb: QPBatch, lr: LowRank, strm, w_min: int = 0):
     """Band Gram of the panel rows + PC / CC tables for pq_lr_capacitance_band, or None when
     the band form does not apply (per-problem constraints, non-uniform box rho, tmax > 1024).
     ``w_min``: band width at least this (the group capacitance needs the widest union span)."""
-    if not qb.shared or lr.tmax > 1024 or not _uniform_box(qb):
+    if not _band_applies(qb, lr):
         return None
     lib = _lib.load()
     r0, nrows, W = lr.span()
@@ -789,151 +796,138 @@ def _band_setup(qb: QPBatch, lr: LowRank, strm, w_min: int = 0):
         C = qb.Cg[0, :mg, :n]
         return (C @ C.T).contiguous() if mg else torch.zeros((1, 1), dtype=F64, device=dev)
     cc = _cached(qb, "_c_cc", _tkey(qb.Cg), cgram, keep=(qb.Cg,))
-    return {"band": band, "ldo": ldo, "r0": r0, "pc": pc, "cc": cc, "W": W, "nrows": nrows}
+    # "cap" / "admm": the argument runs the capacitance kernels / the fused ADMM kernels take
+    return {"band": band, "ldo": ldo, "r0": r0, "pc": pc, "cc": cc, "W": W, "nrows": nrows,
+            "cap": (band.data_ptr(), ldo, r0, pc.data_ptr(), pc.stride(0)),
+            "admm": (pc.data_ptr(), pc.stride(0), r0, cc.data_ptr())}
 
 
-def _gcap_setup(qb: QPBatch, lr: "LowRank", ws: "Workspace", groups: "GroupPlan", settings: Settings):
-    """Buffers and C structs of the group capacitance (admm_gcap.hip), or None when the dates
-    of some group do not share c = p_scale w_scale and p_diag.  Also sets one rho per group
-    (the mean of its dates' initial rho) in ws.rho."""
-    B, dev, mg = qb.batch, qb.device, qb.mg
+def _group_uniform(qb: QPBatch, lr: "LowRank", groups: "GroupPlan") -> bool:
+    """The dates of every group share c = p_scale w_scale and p_diag, so one capacitance per
+    group serves them all (a device fact, checked once per plan and batch)."""
+    B, dev = qb.batch, qb.device
 
     def uniform():
-        ps = qb.p_scale if qb.p_scale is not None else torch.ones(B, dtype=F64, device=dev)
-        wsc = lr.w_scale if lr.w_scale is not None else torch.ones(B, dtype=F64, device=dev)
-        c = ps * wsc
+        one = torch.ones(B, dtype=F64, device=dev)
+        c = (qb.p_scale if qb.p_scale is not None else one) * (lr.w_scale if lr.w_scale is not None else one)
         pd = qb.p_diag if qb.p_diag is not None else torch.zeros(B, dtype=F64, device=dev)
         first = groups.gdates[:-1].long()[groups.gidx.long()]
         return bool(((c == c[first]) & (pd == pd[first])).all().item())
-    if not _cached(ws, "_c_gcap_uniform", (id(groups),) + _tkey(qb.p_scale, lr.w_scale, qb.p_diag), uniform,
-                   keep=(groups, qb.p_scale, lr.w_scale, qb.p_diag)):
-        return None
-    G = groups.ngroups
-    k_ld = round_up(groups.ucnt_max + mg, 64)
-    ldh = min(64, round_up(groups.corr_max, 8))
-    key = (B, G, k_ld, ldh)
-    buf = getattr(ws, "_gcap", None)
-    if buf is None or buf["key"] != key:
-        buf = {"key": key,
-               "M": torch.empty((G, k_ld, k_ld), dtype=F64, device=dev),
-               "Minv": torch.empty((G, k_ld, k_ld), dtype=F64, device=dev),
-               "Dt": torch.empty((G, k_ld // 64, 64, 64), dtype=F64, device=dev),
-               "grho": torch.empty(G, dtype=F64, device=dev),
-               "iters": torch.zeros(G, dtype=torch.int32, device=dev),
-               "status": torch.zeros(G, dtype=torch.int32, device=dev),
-               "info": torch.zeros(G, dtype=torch.int32, device=dev),
-               "aq": torch.empty((B, 2 * k_ld), dtype=F64, device=dev),
-               "hinv": torch.empty((B, ldh, ldh), dtype=F64, device=dev)}
-        ws._gcap = buf
-    # one rho per group: the mean of the dates' initial rho (scale-aware, _rho_floor_q included)
-    gidx, sizes = groups.device_index()
-    gr = buf["grho"]
-    gr.zero_().index_add_(0, gidx, ws.rho)
-    gr /= sizes
-    torch.index_select(gr, 0, gidx, out=ws.rho)
-    kmax = groups.ucnt_max + mg
-    buf["c"] = _lib.PQGcap(gdates=groups.gdates.data_ptr(), ngroups=G, urows=groups.urows.data_ptr(),
-                           ucnt=groups.ucnt.data_ptr(), uoff=groups.uoff.data_ptr(), umax=groups.umax,
-                           gidx=groups.gidx.data_ptr(), grho=buf["grho"].data_ptr(), M=buf["M"].data_ptr(),
-                           Minv=buf["Minv"].data_ptr(), k_ld=k_ld, M_stride=k_ld * k_ld,
-                           aq=buf["aq"].data_ptr(), aq_stride=2 * k_ld, hinv=buf["hinv"].data_ptr(), ldh=ldh,
-                           gmax=int(groups.sizes.max()) if G else 0)
-    # the factor sees each M_U as a k x k "problem" (identity padding beyond its U + mg rows)
-    buf["pb"] = _lib.PQProblem(n=kmax, ld=k_ld, batch=G, mg=0, P=buf["M"].data_ptr(), P_stride=k_ld * k_ld,
-                               q=qb.q.data_ptr(), q_stride=qb.q.stride(0), Cg=qb.Cg.data_ptr(),
-                               lg=qb.lg.data_ptr(), ug=qb.ug.data_ptr())
-    buf["st"] = _lib.PQState(K=buf["Minv"].data_ptr(), K_stride=k_ld * k_ld, Dt=buf["Dt"].data_ptr(),
-                             Dt_stride=(k_ld // 64) * 4096, x=ws.x.data_ptr(), Px=ws.Px.data_ptr(),
-                             z=ws.z.data_ptr(), y=ws.y.data_ptr(), m_ld=ws.m_ld, mg_pad=ws.mg_pad,
-                             rho=buf["grho"].data_ptr(), iters=buf["iters"].data_ptr(),
-                             status=buf["status"].data_ptr(), info=buf["info"].data_ptr(), out=ws.out.data_ptr(),
-                             work=ws.work.data_ptr(), work_stride=ws.work_stride)
-    return buf
+    return _cached(groups, "_c_uniform", (B,) + _tkey(qb.p_scale, lr.w_scale, qb.p_diag), uniform,
+                   keep=(qb.p_scale, lr.w_scale, qb.p_diag))
+
+
+def _matrix_stack(count: int, k_ld: int, dev, nstatus: int | None = None) -> dict:
+    """``count`` k x k matrices M, their inverses Minv, the factor kernels' scratch and per-matrix outputs."""
+    def ints(m):
+        return torch.zeros(m, dtype=torch.int32, device=dev)
+    return {"M": torch.empty((count, k_ld, k_ld), dtype=F64, device=dev),
+            "Minv": torch.empty((count, k_ld, k_ld), dtype=F64, device=dev),
+            "Dt": torch.empty((count, k_ld // 64, 64, 64), dtype=F64, device=dev),
+            "iters": ints(count), "status": ints(nstatus or count), "info": ints(count)}
+
+
+def _factor_view(qb: QPBatch, ws: "Workspace", buf: dict, n: int, rho: torch.Tensor):
+    """(PQProblem, PQState) that present the k x k matrices buf["M"] to the factor kernels as "problems" of
+    size ``n`` (the padded tail of each is the identity: its pivot steps are skipped); inverses to buf["Minv"]."""
+    k_ld = buf["M"].shape[1]
+    pb = _lib.PQProblem(n=n, ld=k_ld, batch=buf["M"].shape[0], mg=0, P=buf["M"].data_ptr(), P_stride=k_ld * k_ld,
+                        q=qb.q.data_ptr(), q_stride=qb.q.stride(0), Cg=qb.Cg.data_ptr(), lg=qb.lg.data_ptr(),
+                        ug=qb.ug.data_ptr())
+    st = ws.c_struct(buf["Minv"], buf["Dt"])
+    st.rho, st.iters, st.status, st.info = (t.data_ptr() for t in (rho, buf["iters"], buf["status"], buf["info"]))
+    return pb, st
+
+
+class GroupCap:
+    """Group capacitance (admm_gcap.hip): one matrix M_U per date group plus every date's low-rank
+    correction a_b, q_b, H_b^-1 -- the buffers, the PQGcap struct and the factor's view of the M_U stack.
+    ``mg`` general rows sit inside the capacitance (the ADMM's; the wide polish rounds' has none).
+    ``old``: the workspace's previous GroupCap of this use; its buffers are taken over while the shapes stay
+    (the workspace keeps the object, and with it the device memory captured graphs point to, alive)."""
+
+    def __init__(self, qb: QPBatch, ws: "Workspace", groups: "GroupPlan", old: "GroupCap | None", mg: int,
+                 nstatus: int | None = None, gmax: int = 0):
+        B, dev, G = qb.batch, qb.device, groups.ngroups
+        kmax = groups.ucnt_max + mg
+        k_ld, ldh = round_up(kmax, 64), min(64, round_up(groups.corr_max, 8))
+        self.key = (B, G, k_ld, ldh)
+        if old is not None and old.key == self.key:
+            buf = old.buf
+        else:
+            buf = dict(_matrix_stack(G, k_ld, dev, nstatus), grho=torch.empty(G, dtype=F64, device=dev),
+                       aq=torch.empty((B, 2 * k_ld), dtype=F64, device=dev),
+                       hinv=torch.empty((B, ldh, ldh), dtype=F64, device=dev))
+        self.buf = buf
+        self.c = _lib.PQGcap(gdates=groups.gdates.data_ptr(), ngroups=G, urows=groups.urows.data_ptr(),
+                             ucnt=groups.ucnt.data_ptr(), uoff=groups.uoff.data_ptr(), umax=groups.umax,
+                             gidx=groups.gidx.data_ptr(), grho=buf["grho"].data_ptr(), M=buf["M"].data_ptr(),
+                             Minv=buf["Minv"].data_ptr(), k_ld=k_ld, M_stride=k_ld * k_ld,
+                             aq=buf["aq"].data_ptr(), aq_stride=2 * k_ld, hinv=buf["hinv"].data_ptr(), ldh=ldh,
+                             gmax=gmax)
+        # the factor sees each M_U as a k x k "problem" (identity padding beyond its U + mg rows)
+        self.pb, self.st = _factor_view(qb, ws, buf, kmax, buf["grho"])
+
+    def build(self, L_, P_, S_, SS, SSf, bd: dict, strm, tag: str = "", large: bool = False,
+              reset_status: bool = False):
+        """One M_U per group at the current group rho (buf["grho"]), its inverse (settings ``SSf``) and every
+        date's a_b, q_b, H_b^-1.  ``reset_status``: the factor and the prepare step share the status buffer."""
+        lib, buf = _lib.load(), self.buf
+        GC_, PM_, SM_ = ctypes.byref(self.c), ctypes.byref(self.pb), ctypes.byref(self.st)
+        _lib.check(lib.pq_gcap_assemble(L_, P_, GC_, SS, *bd["cap"], bd["cc"].data_ptr(), strm),
+                   "pq_gcap_assemble" + tag)
+        if large:   # (experiment) many workgroups per M_U: K2L, one tile each
+            W = buf["W"] = buf["W"] if "W" in buf else torch.empty_like(buf["M"])
+            _lib.check(lib.pq_factor_large(PM_, SM_, None, 0, SSf, 2, W.data_ptr(), W.stride(0), strm),
+                       "pq_factor_large(M_U)")
+        else:
+            _lib.check(lib.pq_factor_batched(PM_, SM_, None, 0, SSf, 2, strm), "pq_factor_batched(M_U)" + tag)
+        if reset_status:
+            buf["status"].zero_()
+        _lib.check(lib.pq_gcap_prepare(L_, P_, S_, GC_, SS, None, 0, *bd["cap"], strm), "pq_gcap_prepare" + tag)
 
 
 def _pg_wide_setup(qb: QPBatch, lr: "LowRank", ws: "Workspace", groups: "GroupPlan", bd: dict, rec: torch.Tensor,
                    settings: Settings, sparse_cols, strm):
     """Group capacitance of the polish matrix K = P + d I for the wide rounds of the grouped
     polish (polish_gw.hip), d = p_diag + delta_g with delta_g the geometric mean of the
-    group's dates' delta (settings.delta x problem scale, record field PQ_PG_SC): the same
-    assemble / factor / prepare as the ADMM's group capacitance, with no general rows in the
-    capacitance and a unit box whose rho is delta_g.  Returns the pq_pg_wide argument
-    (its buffers kept alive on ws), or None when the wide form does not apply."""
-    lib = _lib.load()
+    group's dates' delta (settings.delta x problem scale, record field PQ_PG_SC): the ADMM's
+    GroupCap with no general rows in the capacitance and a unit box whose rho is delta_g.
+    Returns the pq_pg_wide argument (kept alive on ws), or None when the wide form does not apply."""
     B, dev, mg, G = qb.batch, qb.device, qb.mg, groups.ngroups
     nzr, nzv, nzmax = sparse_cols if mg > 4 else (None, None, 0)
     # uncentred windows only (LeastSquares tracking): with a mean column the correction H_b has
     # the entry 1 - (cT/d)(mu'mu - a'q/d), which cancels catastrophically at the polish's small d
     if (lr.mu is not None or bd is None or bd["W"] < groups.span_max or not qb.shared or mg > 24
-            or (mg > 4 and nzmax == 0) or groups.ucnt_max + mg > 320 or groups.corr_max > 64):
+            or (mg > 4 and nzmax == 0) or groups.ucnt_max + mg > 320 or groups.corr_max > 64
+            or not _group_uniform(qb, lr, groups)):
         return None
-    ps = qb.p_scale if qb.p_scale is not None else torch.ones(B, dtype=F64, device=dev)
-    c = ps * (lr.w_scale if lr.w_scale is not None else torch.ones(B, dtype=F64, device=dev))
-    pd = qb.p_diag if qb.p_diag is not None else torch.zeros(B, dtype=F64, device=dev)
-    first = groups.gdates[:-1].long()[groups.gidx.long()]
-    if not bool(((c == c[first]) & (pd == pd[first])).all().item()):
-        return None
-    k_ld = round_up(groups.ucnt_max, 64)
-    ldh = min(64, round_up(groups.corr_max, 8))
-    key = (B, G, k_ld, ldh)
-    buf = getattr(ws, "_pgw", None)
-    if buf is None or buf["key"] != key:
-        buf = {"key": key,
-               "M": torch.empty((G, k_ld, k_ld), dtype=F64, device=dev),
-               "Minv": torch.empty((G, k_ld, k_ld), dtype=F64, device=dev),
-               "Dt": torch.empty((G, k_ld // 64, 64, 64), dtype=F64, device=dev),
-               "grho": torch.empty(G, dtype=F64, device=dev),
-               "iters": torch.zeros(G, dtype=torch.int32, device=dev),
-               "status": torch.zeros(max(G, B), dtype=torch.int32, device=dev),
-               "info": torch.zeros(G, dtype=torch.int32, device=dev),
-               "aq": torch.empty((B, 2 * k_ld), dtype=F64, device=dev),
-               "hinv": torch.empty((B, ldh, ldh), dtype=F64, device=dev),
-               "wscr": torch.empty((B, _lib.pg_wscr(k_ld)), dtype=F64, device=dev),
-               "lb": torch.zeros(2, dtype=F64, device=dev), "ub": torch.ones(2, dtype=F64, device=dev)}
-        ws._pgw = buf
+    gc = ws._pgw = GroupCap(qb, ws, groups, ws._pgw, mg=0, nstatus=max(G, B))
+    buf = gc.buf
+    if "wscr" not in buf:
+        buf.update(wscr=torch.empty((B, _lib.pg_wscr(gc.c.k_ld)), dtype=F64, device=dev),
+                   lb=torch.zeros(2, dtype=F64, device=dev), ub=torch.ones(2, dtype=F64, device=dev))
     gi, sizes = groups.device_index()
     ld = torch.log(torch.clamp(settings.delta_wide * rec[:, _lib.PQ_PG_SC], min=1e-300))
     gl = torch.zeros(G, dtype=F64, device=dev).index_add_(0, gi, ld)
     buf["grho"].copy_(torch.exp(gl / sizes))
-    gc = _lib.PQGcap(gdates=groups.gdates.data_ptr(), ngroups=G, urows=groups.urows.data_ptr(),
-                     ucnt=groups.ucnt.data_ptr(), uoff=groups.uoff.data_ptr(), umax=groups.umax,
-                     gidx=groups.gidx.data_ptr(), grho=buf["grho"].data_ptr(), M=buf["M"].data_ptr(),
-                     Minv=buf["Minv"].data_ptr(), k_ld=k_ld, M_stride=k_ld * k_ld, aq=buf["aq"].data_ptr(),
-                     aq_stride=2 * k_ld, hinv=buf["hinv"].data_ptr(), ldh=ldh)
     # the polish matrix: no general rows in the capacitance, a unit box (rho = delta_g), sigma 0
     pbw = qb.c_struct()
-    pbw.mg = 0
-    pbw.lb, pbw.ub, pbw.box_stride = buf["lb"].data_ptr(), buf["ub"].data_ptr(), 0
-    sw = Settings(sigma=0.0).to_c()
+    pbw.mg, pbw.lb, pbw.ub, pbw.box_stride = 0, buf["lb"].data_ptr(), buf["ub"].data_ptr(), 0
     stw = _lib.PQState(status=buf["status"].data_ptr())
-    L_ = ctypes.byref(lr.c_struct())
-    band, ldo, r0 = bd["band"].data_ptr(), bd["ldo"], bd["r0"]
-    pcp, ldpc = bd["pc"].data_ptr(), bd["pc"].stride(0)
-    _lib.check(lib.pq_gcap_assemble(L_, ctypes.byref(pbw), ctypes.byref(gc), ctypes.byref(sw), band, ldo, r0, pcp,
-                                    ldpc, bd["cc"].data_ptr(), strm), "pq_gcap_assemble (polish)")
-    pbf = _lib.PQProblem(n=groups.ucnt_max, ld=k_ld, batch=G, mg=0, P=buf["M"].data_ptr(), P_stride=k_ld * k_ld,
-                         q=qb.q.data_ptr(), q_stride=qb.q.stride(0), Cg=qb.Cg.data_ptr(), lg=qb.lg.data_ptr(),
-                         ug=qb.ug.data_ptr())
-    stf = _lib.PQState(K=buf["Minv"].data_ptr(), K_stride=k_ld * k_ld, Dt=buf["Dt"].data_ptr(),
-                       Dt_stride=(k_ld // 64) * 4096, x=ws.x.data_ptr(), Px=ws.Px.data_ptr(), z=ws.z.data_ptr(),
-                       y=ws.y.data_ptr(), m_ld=ws.m_ld, mg_pad=ws.mg_pad, rho=buf["grho"].data_ptr(),
-                       iters=buf["iters"].data_ptr(), status=buf["status"].data_ptr(), info=buf["info"].data_ptr(),
-                       out=ws.out.data_ptr(), work=ws.work.data_ptr(), work_stride=ws.work_stride)
-    _lib.check(lib.pq_factor_batched(ctypes.byref(pbf), ctypes.byref(stf), None, 0, ctypes.byref(sw), 2, strm),
-               "pq_factor_batched (polish M_U)")
-    buf["status"].zero_()
-    _lib.check(lib.pq_gcap_prepare(L_, ctypes.byref(pbw), ctypes.byref(stw), ctypes.byref(gc), ctypes.byref(sw),
-                                   None, 0, band, ldo, r0, pcp, ldpc, strm), "pq_gcap_prepare (polish)")
+    SW = ctypes.byref(Settings(sigma=0.0).to_c())
+    gc.build(ctypes.byref(lr.c_struct()), ctypes.byref(pbw), ctypes.byref(stw), SW, SW, bd, strm, tag=" (polish)",
+             reset_status=True)
     # a date whose correction H_b is not SPD to rounding, or whose group's M_U failed, keeps the
     # per-date kernel (state FALLBACK before the first round)
     bad = (buf["status"][:B] == _lib.PQ_NON_CONVEX) | (buf["info"][gi] != 0)
     rec[:, _lib.PQ_PG_STATE] = torch.where(bad & (rec[:, _lib.PQ_PG_STATE] == _lib.PQ_PG_PENDING),
                                            float(_lib.PQ_PG_FALLBACK), rec[:, _lib.PQ_PG_STATE])
-    buf["gc"] = gc
-    buf["wide"] = _lib.PQPgWide(gc=ctypes.pointer(gc), pc=pcp, ldpc=ldpc, r0=r0, cc=bd["cc"].data_ptr(),
-                                nzr=_ptr(nzr), nzv=_ptr(nzv), nzmax=nzmax, wscr=buf["wscr"].data_ptr(),
-                                wscr_stride=buf["wscr"].stride(0), refine_steps=int(settings.refine_wide))
-    return buf["wide"]
+    pc, ldpc, r0, cc = bd["admm"]
+    gc.wide = _lib.PQPgWide(gc=ctypes.pointer(gc.c), pc=pc, ldpc=ldpc, r0=r0, cc=cc, nzr=_ptr(nzr), nzv=_ptr(nzv),
+                            nzmax=nzmax, wscr=buf["wscr"].data_ptr(), wscr_stride=buf["wscr"].stride(0),
+                            refine_steps=int(settings.refine_wide))
+    return gc.wide
 
 
 def loose_stop_eps(settings: Settings, centred: bool, batch: int, mg: int = 1) -> float:
@@ -953,6 +947,253 @@ def loose_stop_eps(settings: Settings, centred: bool, batch: int, mg: int = 1) -
     return eps
 
 
+@dataclass(frozen=True)
+class LowRankRoute:
+    """Which kernels one solve_lowrank call runs, decided once by lowrank_route."""
+    grouped: bool             # the grouped forms apply (grouped_applicable)
+    capacitance: str          # "group", "eig", "band" or "direct" (BatchResult.capacitance)
+    admm: str                 # "gcap", "sweep", "grouped-fused", "grouped-unfused" or "per-problem"
+    plan: "GroupPlan | None"  # the plan the ADMM runs on (groups, or groups.gcap_plan() for "gcap")
+    band: bool                # the band Gram is built
+    band_wmin: int            # its minimum width: every union the group capacitances read
+    polish: str               # "grouped", "per-date" or "none"
+    loose_eps: float          # the loose ADMM stop before the grouped polish (0: off) ...
+    loose_min_iter: int       # ... and its pq_settings.min_iter
+    sync_free: bool           # the caller's sync_free, honoured
+    sparse_cols: tuple = dataclasses.field(default=(None, None, 0), compare=False)   # _sparse_columns
+
+
+def lowrank_route(qb: QPBatch, lr: LowRank, ws: Workspace, groups: "GroupPlan | None", settings: Settings, *,
+                  polish: bool = True, band: bool = True, fuse: bool = True, grouped_polish: bool = True,
+                  gcap: bool = True, wide_polish: bool = True, sync_free: bool = False,
+                  eig: "EigCap | None" = None, sweep: "SweepPlan | None" = None) -> LowRankRoute:
+    """The route of solve_lowrank for these inputs and caller flags.  Two inputs are device facts, read through
+    cached checks (one host sync per batch, none in the steady state): _band_applies and _group_uniform."""
+    k_ld = round_up(lr.tmax + qb.mg, 64)
+    grouped = grouped_applicable(qb, lr, groups, ws)
+    sparse_cols = _sparse_columns(qb) if grouped else (None, None, 0)
+    # group capacitance: shared rows (none, mg = 0, included), register-resident (mg <= 4) or column-sparse
+    # (mg <= 24, <= 4 nonzeros per asset); pass 1 of admm_gcap.hip covers U + mg <= 320 rows
+    gcap_try = (gcap and eig is None and grouped and fuse and qb.shared
+                and (qb.mg <= 4 or (qb.mg <= 24 and sparse_cols[2] > 0))
+                and groups.ucnt_max + qb.mg <= 320 and groups.corr_max <= 64)
+    # its own plan: up to 32 dates per group (GroupPlan.gcap_plan), for register-resident general rows and
+    # (GCAP32_WIDE) the column-sparse wide form; the polish keeps its 16-date groups (polish_plan)
+    gplan = groups
+    if gcap_try and (qb.mg <= 4 or GCAP32_WIDE):
+        g32 = groups.gcap_plan()
+        if g32.ucnt_max + qb.mg <= 320 and g32.corr_max <= 64:
+            gplan = g32
+    use_band = band and _band_applies(qb, lr)
+    # the band must cover every union the capacitances read: the ADMM's groups and the polish's (wide rounds)
+    wmin = (max(gplan.span_max, groups.polish_plan().span_max)
+            if band and (gcap_try or (grouped and wide_polish)) else 0)
+    if gcap_try and use_band and _group_uniform(qb, lr, gplan):
+        cap, admm, plan = "group", "gcap", gplan
+    else:
+        cap = "eig" if eig is not None else ("band" if use_band else "direct")
+        fused = use_band and fuse and qb.mg <= 32   # uniform D + shared Cg: the fused form
+        plan = groups if grouped else None
+        if not grouped:
+            admm = "per-problem"
+        elif fused and sweep is not None and sweep.applicable(qb, lr, k_ld):
+            admm = "sweep"
+        else:
+            admm = "grouped-fused" if fused else "grouped-unfused"
+    pol = "grouped" if (grouped and grouped_polish and ws.ldk >= 64) else "per-date"
+    if not (polish and settings.polish):
+        pol = "none"
+    eps_loose = loose_stop_eps(settings, lr.mu is not None, qb.batch, qb.mg)
+    loose = (pol == "grouped" and (admm == "gcap" or (settings.eps_grouped_percap and grouped and eig is None))
+             and eps_loose > max(settings.eps_abs, settings.eps_rel))
+    return LowRankRoute(grouped=grouped, capacitance=cap, admm=admm, plan=plan, band=use_band, band_wmin=wmin,
+                        polish=pol, loose_eps=eps_loose if loose else 0.0,
+                        loose_min_iter=max(int(settings.min_iter), int(settings.min_iter_grouped)) if loose else 0,
+                        # sync-free: the group capacitance with the grouped polish only
+                        sync_free=bool(sync_free and admm == "gcap" and pol == "grouped"), sparse_cols=sparse_cols)
+
+
+class _LowRankSolve:
+    """One solve_lowrank call: the C structs of its problem and the launches of its route."""
+
+    def __init__(self, qb: QPBatch, lr: LowRank, ws: Workspace, settings: Settings, route: LowRankRoute, tl: _Timeline,
+                 groups, eig, sweep, wide_polish: bool, max_rounds: int, sf_rounds):
+        self.qb, self.lr, self.ws, self.settings, self.route, self.tl = qb, lr, ws, settings, route, tl
+        self.groups, self.eig, self.sweep, self.wide_polish, self.max_rounds, self.sf_rounds = \
+            groups, eig, sweep, wide_polish, max_rounds, sf_rounds
+        self.lib, self.strm = _lib.load(), _stream()
+        self.s, self.sM = settings.to_c(), settings.to_c(sigma=0.0)   # (sM: the capacitances' factor)
+        self.SS, self.SSM = ctypes.byref(self.s), ctypes.byref(self.sM)
+        # the (lowrank, problem, state) arguments of every launch (a byref keeps its struct alive)
+        self.LPS = (ctypes.byref(lr.c_struct()), ctypes.byref(qb.c_struct()), ctypes.byref(ws.c_struct()))
+        k_ld = round_up(lr.tmax + qb.mg, 64)
+        self.M = ws.lr_buffers(k_ld)        # per-date capacitances M and their inverses
+        self.Mcap, self.Minv = ((self.M[k].data_ptr(), k_ld, k_ld * k_ld) for k in ("M", "Minv"))
+        self.bd = self.gc = None            # band Gram (_band_setup) and group capacitance
+        self.sync_free = route.sync_free    # until the flag read hands over to the host-driven repairs
+        self.pg = {}                        # state of the grouped polish pipeline
+        self.refactors = self.launches = self.fallbacks = 0
+
+    def group_cap(self):
+        """The ADMM's GroupCap, one rho per group: the mean of its dates' initial rho (_rho_floor_q included)."""
+        ws, g = self.ws, self.route.plan
+        self.gc = ws._gcap = GroupCap(self.qb, ws, g, ws._gcap, mg=self.qb.mg,
+                                      gmax=int(g.sizes.max()) if g.ngroups else 0)
+        gidx, sizes = g.device_index()
+        gr = self.gc.buf["grho"]
+        gr.zero_().index_add_(0, gidx, ws.rho)
+        gr /= sizes
+        torch.index_select(gr, 0, gidx, out=ws.rho)
+
+    def refactor(self, idx, nidx, SS):
+        """The capacitance inverses at the current rho: every group's (the kernel agreed a new
+        rho per group), or those of problems idx[0..nidx) (None: all)."""
+        lib, bd, strm = self.lib, self.bd, self.strm
+        if self.gc is not None:
+            return self.gc.build(*self.LPS, SS, self.SSM, bd, strm, large=GCAP_FACTOR == "large")
+        if self.eig is not None:   # from the per-date eigendecompositions: no factorisation
+            return self.eig.form(*self.LPS, SS, self.M["Minv"], idx, nidx, strm)
+        if bd is not None:
+            _lib.check(lib.pq_lr_capacitance_band(*self.LPS, _ptr(idx), nidx, SS, *bd["cap"], bd["cc"].data_ptr(),
+                                                  *self.Mcap, strm), "pq_lr_capacitance_band")
+        else:
+            _lib.check(lib.pq_lr_capacitance(*self.LPS, _ptr(idx), nidx, SS, *self.Mcap, strm), "pq_lr_capacitance")
+        view = _factor_view(self.qb, self.ws, self.M, self.lr.tmax + self.qb.mg, self.ws.rho)
+        PM_, SM_ = ctypes.byref(view[0]), ctypes.byref(view[1])
+        _lib.check(lib.pq_factor_batched(PM_, SM_, _ptr(idx), nidx, self.SSM, 1, strm), "pq_factor_batched(M)")
+
+    def admm(self, idx, nidx, SS):
+        """One launch of the route's ADMM entry point with the settings ``SS``."""
+        lib, r, bd, strm, max_iter = self.lib, self.route, self.bd, self.strm, int(self.s.max_iter)
+        if r.admm == "gcap":   # group capacitance (admm_gcap.hip)
+            nzr, nzv, nzmax = r.sparse_cols if self.qb.mg > 4 else (None, None, 0)
+            return lib.pq_admm_lr_gcap(*self.LPS, ctypes.byref(self.gc.c), SS, max_iter, *bd["admm"], _ptr(nzr),
+                                       _ptr(nzv), nzmax, strm)
+        if r.admm == "sweep":   # two chip-wide launches per iteration (admm_sweep.hip)
+            sw = self.sweep
+            scr = sw.buffer(self.qb, lib)
+            return lib.pq_admm_lr_sweep(*self.LPS, *self.Minv, _ptr(sw.gdates), sw.ngroups, SS, max_iter,
+                                        *bd["admm"], int(sw.q_shared), scr.data_ptr(), scr.numel(), strm)
+        if r.grouped:   # every group relaunches; solved dates are skipped inside
+            g, (nzr, nzv, nzmax) = r.plan, r.sparse_cols
+            fused = bd["admm"] if r.admm == "grouped-fused" else (None, 0, 0, None)
+            return lib.pq_admm_lr_grouped(*self.LPS, *self.Minv, _ptr(g.gdates), g.ngroups, _ptr(g.urows),
+                                          _ptr(g.ucnt), _ptr(g.uoff), g.umax, SS, max_iter, *fused, _ptr(nzr),
+                                          _ptr(nzv), nzmax, strm)
+        return lib.pq_admm_lr_batched(*self.LPS, *self.Minv, _ptr(idx), nidx, SS, max_iter, strm)
+
+    def admm_rounds(self, idx, nidx, SS, name="admm"):
+        """Launch, collect NEED_REFACTOR, refactor, repeat."""
+        for _ in range(self.max_rounds):
+            _lib.check(self.tl(name, lambda: self.admm(idx, nidx, SS)), "pq_admm_lr")
+            self.launches += 1
+            if self.sync_free:   # NEED_REFACTOR is caught by the flag at the end
+                break
+            need = torch.nonzero(self.ws.status == _lib.PQ_NEED_REFACTOR).flatten().to(torch.int32)
+            kk = int(need.numel())
+            if kk == 0:
+                break
+            idx, nidx = need.contiguous(), kk
+            self.tl("factor", lambda: self.refactor(idx, nidx, SS))
+            self.refactors += kk
+
+    def polish_w(self, idx, nidx, SS, name="polish"):
+        """The per-date window-form polish of problems idx[0..nidx) (None: all)."""
+        lib, qb, ws, tl, strm = self.lib, self.qb, self.ws, self.tl, self.strm
+        L_, P_, S_ = self.LPS
+        ldk, kmax = ws.ldk, min(qb.ld, 1024)
+        final = ldk >= kmax
+        bk = self.bd["cap"][:3] if self.bd is not None else (None, 0, 0)
+        _lib.check(tl(name, lambda: lib.pq_polish_w_batched(L_, P_, S_, _ptr(idx), nidx, SS, ldk, int(final),
+                                                            *bk, strm)), "pq_polish_w_batched")
+        if not final:   # free sets larger than the compact scratch: relaunch those with ldk = kmax
+            over = torch.nonzero(ws.out[:, _lib.PQ_OUT_ROUNDS] < 0).flatten().to(torch.int32)
+            m = int(over.numel())   # host sync: small vector
+            if m:
+                K2 = torch.empty((m, kmax, kmax), dtype=F64, device=qb.device)
+                D2 = torch.empty((m, kmax // 64, 64, 64), dtype=F64, device=qb.device)
+                st2 = ws.c_struct(K2, D2)
+                over = over.contiguous()
+                _lib.check(tl(name, lambda: lib.pq_polish_w_batched(L_, P_, ctypes.byref(st2), _ptr(over), m,
+                                                                    SS, kmax, 1, *bk, strm)),
+                           "pq_polish_w_batched (relaunch)")
+
+    def pg_start(self, allow_wide: bool):
+        """k_pg_init (classification from the ADMM point) + the wide rounds' capacitance."""
+        qb, ws = self.qb, self.ws
+        rec = ws.pg_record()
+        g = self.groups.polish_plan()
+        _lib.check(self.lib.pq_polish_grouped_init(*self.LPS, rec.data_ptr(), self.SS, self.strm),
+                   "pq_polish_grouped_init")
+        if ws._pg_pass is None or ws._pg_pass.numel() < g.ngroups * _lib.PQ_PG_PASS_SCRATCH:
+            ws._pg_pass = torch.empty(g.ngroups * _lib.PQ_PG_PASS_SCRATCH, dtype=F64, device=qb.device)
+        # free sets beyond the LDS solve (k_pg_init left each date's free count in PQ_PG_K): the
+        # wide rounds' group capacitance, built once for the whole polish
+        wide = None
+        if allow_wide and self.wide_polish and bool((rec[:, _lib.PQ_PG_K] > min(ws.ldk, 128)).any()):   # host sync
+            wide = _pg_wide_setup(qb, self.lr, ws, g, self.bd, rec, self.settings, self.route.sparse_cols, self.strm)
+        # (the state a replayed sync-free stage hands back: rounds run, the record, a round's arguments)
+        self.pg = dict(rounds=0, rec=rec, keep=(g, wide), round=(
+            *self.LPS, rec.data_ptr(), ws.ldk, _ptr(g.gdates), g.ngroups, _ptr(g.urows), _ptr(g.ucnt), _ptr(g.uoff),
+            g.umax, self.SS, ws._pg_pass.data_ptr(), ctypes.byref(wide) if wide is not None else None, self.strm))
+
+    def pg_round(self):
+        _lib.check(self.lib.pq_polish_grouped_round(*self.pg["round"]), "pq_polish_grouped_round")
+        self.pg["rounds"] += 1
+
+    def pg_rounds_host(self):
+        """The remaining rounds, each followed by a host check for dates still pending."""
+        rec = self.pg["rec"]
+        while self.pg["rounds"] < int(self.s.polish_rounds):
+            if self.pg["rounds"] >= 2 and not bool((rec[:, _lib.PQ_PG_STATE] == _lib.PQ_PG_PENDING).any()):   # sync
+                break
+            self.pg_round()
+
+    def polish_grouped(self):
+        """Grouped polish pipeline (polish_g.hip) for every date; the dates it hands back take the per-date one."""
+        self.pg_start(True)
+        self.pg_round()
+        self.pg_rounds_host()
+        self.pg_finish()
+
+    def polish_sync_free(self):
+        """The grouped polish with a fixed number of rounds and no host check (dates done early skip the later
+        rounds' kernels), then one device flag in ws._sf_flag: anything left for the host-driven repairs (dates
+        pending, handed back or rejected, or an ADMM refactor).  Returns the pipeline state (a copy)."""
+        ws, rounds = self.ws, int(self.s.polish_rounds)
+        self.pg_start(False)
+        for _ in range(min(int(self.sf_rounds or rounds), rounds)):
+            self.pg_round()
+        st_pg = self.pg["rec"][:, _lib.PQ_PG_STATE]
+        flag = ((st_pg == _lib.PQ_PG_PENDING) | (st_pg == _lib.PQ_PG_FALLBACK) |
+                (ws.status == _lib.PQ_NEED_REFACTOR) | (ws.status == _lib.PQ_SOLVED_INACCURATE) |
+                (ws.status == _lib.PQ_UNSOLVED)).any()
+        if ws._sf_flag is None:
+            ws._sf_flag = torch.zeros((), dtype=torch.bool, device=ws.device)
+        ws._sf_flag.copy_(flag)
+        return dict(self.pg)
+
+    def pg_finish(self):
+        """The dates the pipeline handed back: the per-date polish from their ADMM point."""
+        ws = self.ws
+        fb = torch.nonzero(self.pg["rec"][:, _lib.PQ_PG_STATE] == _lib.PQ_PG_FALLBACK).flatten().to(torch.int32)
+        m = self.fallbacks = int(fb.numel())
+        if m:
+            ws.pg_fallback = fb   # (diagnostics)
+            if self.route.loose_eps > 0:   # stopped at the loose eps: resume those to eps first
+                ws.status[fb.long()] = _lib.PQ_UNSOLVED
+                self.admm_rounds(fb.contiguous(), m, self.SS, name="admm (resume, inside polish)")
+            # two refinement steps per round for the hand-offs (vertex cycling, failed
+            # factorisations): config 5's fallback polish 31.3 -> 7.5 ms
+            # (profiles/r02k_bench_config5_qrel30.log -> r02l_bench_config5_fallback_refine2.log)
+            sfb = self.settings.to_c(refine_iters=max(self.settings.refine_iters, 2))
+            self.polish_w(fb.contiguous(), m, ctypes.byref(sfb), name="polish (fallback, inside polish)")
+
+    def result(self) -> BatchResult:
+        return _batch_result(self.qb, self.ws, refactors=self.refactors, admm_launches=self.launches,
+                             polish_fallbacks=self.fallbacks, capacitance=self.route.capacitance)
+
+
 def solve_lowrank(qb: QPBatch, lr: LowRank, settings: Settings | None = None,
                   ws: Workspace | None = None, max_rounds: int = 64, events: list | None = None,
                   polish: bool = True, groups: "GroupPlan | None" = None, band: bool = True,
@@ -963,7 +1204,8 @@ def solve_lowrank(qb: QPBatch, lr: LowRank, settings: Settings | None = None,
     """Woodbury-form solve for T + mg < n: K2 = capacitance SYRK + Cholesky/inverse of the
     k x k matrices M, K3 = low-rank ADMM over the shared window rows (grouped over sliding
     windows when a GroupPlan is given), K4 = window-form polish.  qb.P is never read (it
-    may be None): P is the window (lr) throughout.
+    may be None): P is the window (lr) throughout.  Which kernels run is decided once, by
+    lowrank_route.
 
     ``sync_free`` (group capacitance with the grouped polish, no wide rounds): the stages
     run without any host synchronisation -- one ADMM launch, ``sf_rounds`` polish rounds
@@ -976,317 +1218,72 @@ def solve_lowrank(qb: QPBatch, lr: LowRank, settings: Settings | None = None,
     device works, just before the flag read.  ``sweep`` (SweepPlan: groups of up to 64
     problems sharing one window, porqua_amd.sweep): the fused ADMM runs as pq_admm_lr_sweep
     (two chip-wide launches per iteration) instead of one workgroup per group."""
-    if sync_free and not (gcap and eig is None and groups is not None and grouped_polish and polish):
-        sync_free = False
-    tl = _Timeline(events, graphs if sync_free else None)
+    settings = settings or Settings()
+    ws = ws or Workspace(qb, dense=False)
+    if not lowrank_applicable(qb, lr):
+        raise _lib.PorquaHipError(f"low-rank form not applicable (k={lr.tmax + qb.mg}, n={qb.n})")
+    route = lowrank_route(qb, lr, ws, groups, settings, polish=polish, band=band, fuse=fuse,
+                          grouped_polish=grouped_polish, gcap=gcap, wide_polish=wide_polish, sync_free=sync_free,
+                          eig=eig, sweep=sweep)
+    tl = _Timeline(events, graphs if route.sync_free else None)
     if tl.graphs is not None:
         tl.graphs.begin()
-    lib = _lib.load()
-    s = (settings or Settings()).to_c()
-    ws = ws or Workspace(qb, dense=False)
-    ws.sweep_admm = None   # set below when pq_admm_lr_sweep runs (a reused workspace must not keep it)
-    B, dev = qb.batch, qb.device
-    ldk = ws.ldk
-    k = lr.tmax + qb.mg
-    k_ld = round_up(k, 64)
-    if not lowrank_applicable(qb, lr):
-        raise _lib.PorquaHipError(f"low-rank form not applicable (k={k}, n={qb.n})")
-    M = ws.lr_buffers(k_ld)
-    pb = qb.c_struct()
-    st = ws.c_struct()
-    lrs = lr.c_struct()
-    # n = k: the padded tail of M is the identity, so the factor skips its pivot steps
-    pbM = _lib.PQProblem(n=k, ld=k_ld, batch=B, mg=0, P=M["M"].data_ptr(), P_stride=k_ld * k_ld,
-                         q=qb.q.data_ptr(), q_stride=qb.q.stride(0), Cg=qb.Cg.data_ptr(), lg=qb.lg.data_ptr(),
-                         ug=qb.ug.data_ptr())
-    stM = _lib.PQState(K=M["Minv"].data_ptr(), K_stride=k_ld * k_ld, Dt=M["Dt"].data_ptr(),
-                       Dt_stride=(k_ld // 64) * 4096, x=ws.x.data_ptr(), Px=ws.Px.data_ptr(),
-                       z=ws.z.data_ptr(), y=ws.y.data_ptr(), m_ld=ws.m_ld, mg_pad=ws.mg_pad,
-                       rho=ws.rho.data_ptr(), iters=M["iters"].data_ptr(), status=M["status"].data_ptr(),
-                       info=M["info"].data_ptr(), out=ws.out.data_ptr(), work=ws.work.data_ptr(),
-                       work_stride=ws.work_stride)
-    sM = (settings or Settings()).to_c()
-    sM.sigma = 0.0
-    strm = _stream()
-    P_, S_, SS, L_ = ctypes.byref(pb), ctypes.byref(st), ctypes.byref(s), ctypes.byref(lrs)
-    PM_, SM_, SSM = ctypes.byref(pbM), ctypes.byref(stM), ctypes.byref(sM)
-    _lib.check(lib.pq_init_state_lr(L_, P_, S_, None, 0, SS, strm), "pq_init_state_lr")
-    _rho_floor_q(qb, ws, settings or Settings())
-
-    bd = None
-
-    def refactor(idx, nidx):
-        if eig is not None:   # from the per-date eigendecompositions: no factorisation
-            eig.form(L_, P_, S_, SS, M["Minv"], idx, nidx, strm)
-            return
-        if bd is not None:
-            _lib.check(lib.pq_lr_capacitance_band(L_, P_, S_, _ptr(idx), nidx, SS, bd["band"].data_ptr(), bd["ldo"],
-                                                  bd["r0"], bd["pc"].data_ptr(), bd["pc"].stride(0),
-                                                  bd["cc"].data_ptr(), M["M"].data_ptr(), k_ld, k_ld * k_ld, strm),
-                       "pq_lr_capacitance_band")
-        else:
-            _lib.check(lib.pq_lr_capacitance(L_, P_, S_, _ptr(idx), nidx, SS, M["M"].data_ptr(), k_ld,
-                                             k_ld * k_ld, strm), "pq_lr_capacitance")
-        _lib.check(lib.pq_factor_batched(PM_, SM_, _ptr(idx), nidx, SSM, 1, strm), "pq_factor_batched(M)")
-
-    grouped = grouped_applicable(qb, lr, groups, ws)
-    sparse_cols = _sparse_columns(qb) if grouped else (None, None, 0)
-    # group capacitance: shared rows, register-resident (mg <= 4) or column-sparse (mg <= 24,
-    # <= 4 nonzeros per asset); pass 1 of admm_gcap.hip covers U + mg <= 320 rows
-    # (box-only problems, mg = 0, included: k_admm_gcap<0> once read an undefined Cg register
-    # and stopped every date after one iteration; fixed, tests/test_gcap_gpu.py)
-    gcap_try = (gcap and eig is None and grouped and fuse and qb.shared
-                and (qb.mg <= 4 or (qb.mg <= 24 and sparse_cols[2] > 0))
-                and groups.ucnt_max + qb.mg <= 320 and groups.corr_max <= 64)
-    # the group capacitance's own plan: up to 32 dates per group (GroupPlan.gcap_plan), for
-    # register-resident general rows and (GCAP32_WIDE) the column-sparse wide form; the polish
-    # keeps its 16-date groups (polish_plan)
-    gplan = groups
-    if gcap_try and (qb.mg <= 4 or GCAP32_WIDE):
-        g32 = groups.gcap_plan()
-        if g32.ucnt_max + qb.mg <= 320 and g32.corr_max <= 64:
-            gplan = g32
+    c = _LowRankSolve(qb, lr, ws, settings, route, tl, groups, eig, sweep, wide_polish, max_rounds, sf_rounds)
+    # what bench.py and the tests read: the plan and the kernel the ADMM runs on
+    ws.gcap_groups = route.plan if route.admm == "gcap" else None
+    ws.sweep_admm = sweep if route.admm == "sweep" else None
+    ws.pg_fallback = None
+    _lib.check(c.lib.pq_init_state_lr(*c.LPS, None, 0, c.SS, c.strm), "pq_init_state_lr")
+    _rho_floor_q(qb, ws, settings)
     if band:
-        # the band must cover every union the capacitances read: the ADMM's groups and the
-        # polish's (wide rounds)
-        wmin = (max(gplan.span_max, groups.polish_plan().span_max) if (gcap_try or (grouped and wide_polish))
-                else 0)
-        bd = tl("gram", lambda: _band_setup(qb, lr, strm, w_min=wmin))
-        ws.band_shape = (bd["nrows"], bd["W"]) if bd is not None else None   # (the bench's gram rate)
-    gc = _gcap_setup(qb, lr, ws, gplan, settings or Settings()) if (gcap_try and bd is not None) else None
-    ws.gcap_groups = gplan if gc is not None else None   # (the bench's roofline reads the plan used)
+        c.bd = tl("gram", lambda: _band_setup(qb, lr, c.strm, w_min=route.band_wmin))
+    ws.band_shape = (c.bd["nrows"], c.bd["W"]) if c.bd is not None else None   # (the bench's gram rate)
+    if route.admm == "gcap":
+        c.group_cap()
+    tl("factor", lambda: c.refactor(None, 0, c.SS))
 
-    def refactor_groups():
-        """Group capacitance: one M_U per group (current group rho), its inverse, and every
-        date's a_b, q_b, H_b^-1."""
-        g = gc
-        GC_ = ctypes.byref(g["c"])
-        _lib.check(lib.pq_gcap_assemble(L_, P_, GC_, SS, bd["band"].data_ptr(), bd["ldo"], bd["r0"],
-                                        bd["pc"].data_ptr(), bd["pc"].stride(0), bd["cc"].data_ptr(), strm),
-                   "pq_gcap_assemble")
-        if GCAP_FACTOR == "large":   # (experiment) many workgroups per M_U: K2L, one tile each
-            if g.get("W") is None:
-                g["W"] = torch.empty_like(g["M"])
-            _lib.check(lib.pq_factor_large(ctypes.byref(g["pb"]), ctypes.byref(g["st"]), None, 0, SSM, 2,
-                                           g["W"].data_ptr(), g["W"].stride(0), strm), "pq_factor_large(M_U)")
-        else:
-            _lib.check(lib.pq_factor_batched(ctypes.byref(g["pb"]), ctypes.byref(g["st"]), None, 0, SSM, 2, strm),
-                       "pq_factor_batched(M_U)")
-        _lib.check(lib.pq_gcap_prepare(L_, P_, S_, GC_, SS, None, 0, bd["band"].data_ptr(), bd["ldo"], bd["r0"],
-                                       bd["pc"].data_ptr(), bd["pc"].stride(0), strm), "pq_gcap_prepare")
-
-    if gc is not None:
-        tl("factor", refactor_groups)
-    else:
-        tl("factor", lambda: refactor(None, 0))
-
-    def admm(idx, nidx):
-        if gc is not None:   # group capacitance (admm_gcap.hip)
-            nzr, nzv, nzmax = sparse_cols if qb.mg > 4 else (None, None, 0)
-            return lib.pq_admm_lr_gcap(L_, P_, S_, ctypes.byref(gc["c"]), SS, int(s.max_iter), bd["pc"].data_ptr(),
-                                       bd["pc"].stride(0), bd["r0"], bd["cc"].data_ptr(), _ptr(nzr), _ptr(nzv),
-                                       nzmax, strm)
-        if grouped:   # every group relaunches; solved dates are skipped inside
-            fz = bd is not None and fuse and qb.mg <= 32   # uniform D + shared Cg: the fused form
-            if fz and sweep is not None and sweep.applicable(qb, lr, k_ld):
-                ws.sweep_admm = sweep   # (the bench's roofline reads which kernel ran)
-                scr = sweep.buffer(qb, lib)
-                return lib.pq_admm_lr_sweep(L_, P_, S_, M["Minv"].data_ptr(), k_ld, k_ld * k_ld,
-                                            _ptr(sweep.gdates), sweep.ngroups, SS, int(s.max_iter),
-                                            bd["pc"].data_ptr(), bd["pc"].stride(0), bd["r0"], bd["cc"].data_ptr(),
-                                            int(sweep.q_shared), scr.data_ptr(), scr.numel(), strm)
-            nzr, nzv, nzmax = sparse_cols
-            return lib.pq_admm_lr_grouped(L_, P_, S_, M["Minv"].data_ptr(), k_ld, k_ld * k_ld,
-                                          _ptr(groups.gdates), groups.ngroups, _ptr(groups.urows),
-                                          _ptr(groups.ucnt), _ptr(groups.uoff), groups.umax, SS,
-                                          int(s.max_iter), bd["pc"].data_ptr() if fz else None,
-                                          bd["pc"].stride(0) if fz else 0, bd["r0"] if fz else 0,
-                                          bd["cc"].data_ptr() if fz else None, _ptr(nzr), _ptr(nzv), nzmax,
-                                          strm)
-        return lib.pq_admm_lr_batched(L_, P_, S_, M["Minv"].data_ptr(), k_ld, k_ld * k_ld, _ptr(idx),
-                                      nidx, SS, int(s.max_iter), strm)
-
-    cnt = {"refactors": 0, "launches": 0, "pg_fallback": 0}
-    if sync_free and gc is None:   # the group capacitance did not apply: host-driven solve
-        sync_free = False
-        tl.graphs = None
-
-    def admm_rounds(idx, nidx, SSx, name="admm"):
-        nonlocal SS
-        SS0, SS = SS, SSx   # admm() reads SS
-        for _ in range(max_rounds):
-            _lib.check(tl(name, lambda: admm(idx, nidx)), "pq_admm_lr")
-            cnt["launches"] += 1
-            if sync_free:   # NEED_REFACTOR is caught by the flag at the end
-                break
-            need = torch.nonzero(ws.status == _lib.PQ_NEED_REFACTOR).flatten().to(torch.int32)
-            kk = int(need.numel())
-            if kk == 0:
-                break
-            idx, nidx = need.contiguous(), kk
-            if gc is not None:    # the kernel agreed a new rho per group: rebuild every M_U
-                tl("factor", refactor_groups)
-            else:
-                tl("factor", lambda: refactor(idx, nidx))
-            cnt["refactors"] += kk
-        SS = SS0
-
-    def polish_w(idx, nidx, SSp=None, name="polish"):
-        SS = SSp if SSp is not None else SS_main
-        kmax = min(qb.ld, 1024)
-        final = ldk >= kmax
-        bk = (bd["band"].data_ptr(), bd["ldo"], bd["r0"]) if bd is not None else (None, 0, 0)
-        _lib.check(tl(name, lambda: lib.pq_polish_w_batched(L_, P_, S_, _ptr(idx), nidx, SS, ldk, int(final),
-                                                                *bk, strm)), "pq_polish_w_batched")
-        if not final:   # free sets larger than the compact scratch: relaunch those with ldk = kmax
-            over = torch.nonzero(ws.out[:, _lib.PQ_OUT_ROUNDS] < 0).flatten().to(torch.int32)
-            m = int(over.numel())   # host sync: small vector
-            if m:
-                K2 = torch.empty((m, kmax, kmax), dtype=F64, device=dev)
-                D2 = torch.empty((m, kmax // 64, 64, 64), dtype=F64, device=dev)
-                st2 = ws.c_struct()
-                st2.K, st2.K_stride = K2.data_ptr(), K2.stride(0)
-                st2.Dt, st2.Dt_stride = D2.data_ptr(), D2.stride(0)
-                over = over.contiguous()
-                _lib.check(tl(name, lambda: lib.pq_polish_w_batched(L_, P_, ctypes.byref(st2), _ptr(over), m,
-                                                                        SS, kmax, 1, *bk, strm)),
-                           "pq_polish_w_batched (relaunch)")
-
-    pg = {}
-
-    def pg_start(allow_wide: bool):
-        """k_pg_init (classification from the ADMM point) + the wide rounds' capacitance."""
-        rec = ws.pg_record()
-        g = groups.polish_plan()
-        _lib.check(lib.pq_polish_grouped_init(L_, P_, S_, rec.data_ptr(), SS_main, strm), "pq_polish_grouped_init")
-        scr = getattr(ws, "_pg_pass", None)
-        if scr is None or scr.numel() < g.ngroups * _lib.PQ_PG_PASS_SCRATCH:
-            scr = torch.empty(g.ngroups * _lib.PQ_PG_PASS_SCRATCH, dtype=F64, device=dev)
-            ws._pg_pass = scr
-        # free sets beyond the LDS solve (k_pg_init left each date's free count in PQ_PG_K): the
-        # wide rounds' group capacitance, built once for the whole polish
-        wide = None
-        if allow_wide and wide_polish and bool((rec[:, _lib.PQ_PG_K] > min(ldk, 128)).any()):   # host sync
-            wide = _pg_wide_setup(qb, lr, ws, g, bd, rec, settings or Settings(), sparse_cols, strm)
-        cnt["pg_wide"] = wide is not None
-        pg.update(rec=rec, g=g, scr=scr, wide=wide, wide_p=ctypes.byref(wide) if wide is not None else None,
-                  rounds=0)
-
-    def pg_round():
-        g, rec = pg["g"], pg["rec"]
-        _lib.check(lib.pq_polish_grouped_round(L_, P_, S_, rec.data_ptr(), ldk, _ptr(g.gdates), g.ngroups,
-                                               _ptr(g.urows), _ptr(g.ucnt), _ptr(g.uoff), g.umax, SS_main,
-                                               pg["scr"].data_ptr(), pg["wide_p"], strm), "pq_polish_grouped_round")
-        pg["rounds"] += 1
-
-    def pg_rounds_host():
-        """The remaining rounds, each followed by a host check for dates still pending."""
-        rec = pg["rec"]
-        while pg["rounds"] < int(s.polish_rounds):
-            if pg["rounds"] >= 2 and not bool((rec[:, _lib.PQ_PG_STATE] == _lib.PQ_PG_PENDING).any()):   # sync
-                break
-            pg_round()
-
-    def polish_grouped():
-        """Grouped polish pipeline (polish_g.hip) for every date; the dates it hands back
-        (FALLBACK) go through pq_polish_w_batched from their ADMM point."""
-        pg_start(True)
-        pg_round()
-        pg_rounds_host()
-        pg_finish()
-
-    def polish_sync_free():
-        """The grouped polish with a fixed number of rounds and no host check (dates done
-        early skip the later rounds' kernels), then one device flag: anything left for the
-        host-driven repairs (dates pending, handed back or rejected, or an ADMM refactor)."""
-        pg_start(False)
-        for _ in range(min(int(sf_rounds or s.polish_rounds), int(s.polish_rounds))):
-            pg_round()
-        st_pg = pg["rec"][:, _lib.PQ_PG_STATE]
-        flag = ((st_pg == _lib.PQ_PG_PENDING) | (st_pg == _lib.PQ_PG_FALLBACK) |
-                (ws.status == _lib.PQ_NEED_REFACTOR) | (ws.status == _lib.PQ_SOLVED_INACCURATE) |
-                (ws.status == _lib.PQ_UNSOLVED)).any()
-        if getattr(ws, "_sf_flag", None) is None:
-            ws._sf_flag = torch.zeros((), dtype=torch.bool, device=dev)
-        ws._sf_flag.copy_(flag)
-        return dict(pg)   # the pipeline state (a replayed graph does not run this function)
-
-    def pg_finish():
-        rec = pg["rec"]
-        fb = torch.nonzero(rec[:, _lib.PQ_PG_STATE] == _lib.PQ_PG_FALLBACK).flatten().to(torch.int32)
-        m = int(fb.numel())
-        cnt["pg_fallback"] = m
-        if m:
-            ws.pg_fallback = fb   # the dates handed to the per-date kernel (diagnostics)
-            if SS_admm is not SS_main:   # stopped at eps_grouped: resume those to eps first
-                ws.status[fb.long()] = _lib.PQ_UNSOLVED
-                admm_rounds(fb.contiguous(), m, SS_main, name="admm (resume, inside polish)")
-            # two refinement steps per round for the hand-offs (vertex cycling, failed
-            # factorisations): config 5's fallback polish 31.3 -> 7.5 ms
-            # (profiles/r02k_bench_config5_qrel30.log -> r02l_bench_config5_fallback_refine2.log)
-            sfb = type(s).from_buffer_copy(s)
-            sfb.refine_iters = max(sfb.refine_iters, 2)
-            polish_w(fb.contiguous(), m, ctypes.byref(sfb), name="polish (fallback, inside polish)")
-
-    SS_main = SS
-    SS_admm = SS
-    st_ = settings or Settings()
-    eps_loose = loose_stop_eps(st_, lr.mu is not None, qb.batch, qb.mg)
-    if ((gc is not None or (st_.eps_grouped_percap and grouped and eig is None)) and polish and s.polish
-            and grouped_polish and ldk >= 64 and eps_loose > max(st_.eps_abs, st_.eps_rel)):
-        sl = st_.to_c()
-        sl.eps_abs = sl.eps_rel = eps_loose
-        sl.min_iter = max(int(st_.min_iter), int(st_.min_iter_grouped))
+    SS_admm = c.SS
+    if route.loose_eps > 0:   # the ADMM only has to predict the active set for the grouped polish
+        sl = settings.to_c(eps_abs=route.loose_eps, eps_rel=route.loose_eps, min_iter=route.loose_min_iter)
         SS_admm = ctypes.byref(sl)
-    if sync_free and not (grouped and ldk >= 64 and s.polish):
-        sync_free = False
-        tl.graphs = None
-    admm_rounds(None, 0, SS_admm)
-    if sync_free:
-        pg.update(tl("polish", polish_sync_free))
+    c.admm_rounds(None, 0, SS_admm)
+
+    if c.sync_free:
+        c.pg = dict(tl("polish", c.polish_sync_free))   # (a replayed graph does not run the function)
         if host_work is not None:
             host_work()
         if not bool(ws._sf_flag.item()):   # the one host sync of the step: nothing left to repair
-            return _lowrank_result(qb, ws, cnt, "group")
+            return c.result()
         if bool((ws.status == _lib.PQ_NEED_REFACTOR).any() | (ws.status == _lib.PQ_UNSOLVED).any()):
-            # an adaptive-rho refactorisation was requested: redo the whole solve host-driven
-            return solve_lowrank(qb, lr, settings, ws, max_rounds, events, polish, groups, band, fuse,
-                                 grouped_polish, gcap, eig, wide_polish)
-        tl.graphs = None   # the repairs below are host-driven
-        sync_free = False  # (admm_rounds checks for refactorisations again)
-        pg_rounds_host()   # dates still pending: the remaining rounds
-        pg_finish()        # dates handed back: the per-date polish
-        polished = True
-    else:
-        polished = False
-    if s.polish and polish:
-        if not polished:
-            if grouped and grouped_polish and ldk >= 64:
-                tl("polish", polish_grouped)
-            else:
-                polish_w(None, 0)
+            # an adaptive-rho refactorisation was requested: redo the whole solve host-driven.
+            # Not forwarded: sync_free, graphs and sf_rounds (the redo is the host-driven solve),
+            # host_work (it ran above) and sweep (the redo takes the group capacitance again,
+            # which has no sweep form)
+            return solve_lowrank(qb, lr, settings=settings, ws=ws, max_rounds=max_rounds, events=events,
+                                 polish=polish, groups=groups, band=band, fuse=fuse, grouped_polish=grouped_polish,
+                                 gcap=gcap, eig=eig, wide_polish=wide_polish)
+        tl.graphs = None       # the repairs below are host-driven
+        c.sync_free = False    # (admm_rounds checks for refactorisations again)
+        c.pg_rounds_host()     # dates still pending: the remaining rounds
+        c.pg_finish()          # dates handed back: the per-date polish
+    elif route.polish == "grouped":
+        tl("polish", c.polish_grouped)
+    elif route.polish == "per-date":
+        c.polish_w(None, 0, c.SS)
+    if route.polish != "none":
         # one host sync: nothing rejected (the usual case) skips both repairs
         rejected = bool((ws.status == _lib.PQ_SOLVED_INACCURATE).any().item())
-        rp = _repolish_set(ws, settings or Settings()) if rejected else None
+        rp = _repolish_set(ws, settings) if rejected else None
         if rp is not None:      # polish rejected: polish again with more refinement steps
             pidx, pn, s3 = rp
-            polish_w(pidx, pn, ctypes.byref(s3))
-        retry = _retry_set(ws, settings or Settings()) if rejected else None
+            c.polish_w(pidx, pn, ctypes.byref(s3))
+        retry = _retry_set(ws, settings) if rejected else None
         if retry is not None:   # polish rejected: resume ADMM to eps_retry, polish again
             ridx, rn, s2 = retry
-            admm_rounds(ridx, rn, ctypes.byref(s2))
-            s4 = (settings or Settings()).to_c()
-            s4.refine_iters = max(s4.refine_iters, (settings or Settings()).refine_retry)
-            polish_w(ridx, rn, ctypes.byref(s4))
-    return _lowrank_result(qb, ws, cnt, "group" if gc is not None else ("eig" if eig is not None else
-                                                                       ("band" if bd is not None else "direct")))
-
-
-def _lowrank_result(qb: QPBatch, ws: Workspace, cnt: dict, capacitance: str) -> BatchResult:
-    n, mg = qb.n, qb.mg
-    return BatchResult(x=ws.x[:, :n], y=ws.y[:, :mg], z_box=ws.y[:, ws.mg_pad:ws.mg_pad + n],
-                       status=ws.status, iters=ws.iters, out=ws.out, refactors=cnt["refactors"],
-                       admm_launches=cnt["launches"], polish_fallbacks=cnt["pg_fallback"], capacitance=capacitance)
+            c.admm_rounds(ridx, rn, ctypes.byref(s2))
+            s4 = settings.to_c(refine_iters=max(settings.refine_iters, settings.refine_retry))
+            c.polish_w(ridx, rn, ctypes.byref(s4))
+    return c.result()
 
 
 def factor_only(qb: QPBatch, invert: bool = False, sigma: float = 0.0):
@@ -1614,6 +1611,7 @@ class Panel:
         self.R = R.to(self.device, dtype=F64).contiguous()
         self.D, self.n = self.R.shape
         self.bm = None
+        self._has_nan = None
         if bm is not None:
             y = bm if isinstance(bm, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(bm, dtype=np.float64).reshape(-1))
             self.bm = y.to(self.device, dtype=F64).contiguous()
@@ -1677,7 +1675,7 @@ class Panel:
 
     @property
     def has_nan(self) -> bool:
-        if getattr(self, "_has_nan", None) is None:
+        if self._has_nan is None:
             self._has_nan = bool(torch.isnan(self.R).any().item())
         return self._has_nan
 

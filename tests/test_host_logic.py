@@ -506,3 +506,148 @@ def test_window_rows_without_rebalance_dates():
         assert tlen.shape == (0,) and tlen.dtype == np.int32
     rows, tlen = engine.window_rows(dates, dates[[9, 20]], 10)   # (the fast path itself still runs)
     assert tlen.tolist() == [10, 10] and np.array_equal(rows[1], np.arange(11, 21))
+
+
+# ---- engine.lowrank_route: which kernels solve_lowrank runs, on CPU tensors ------------------
+
+def _route_problem(mg=1, shared=True, rows_kind="sparse", uniform=True, centred=True, cus=256):
+    """tests/test_gcap_gpu.py::_problem at n = 300, T = 60, D = 40, stride 1, on the CPU: the
+    batch, a stub of the window (what the route reads of it), the GroupPlan and a Workspace."""
+    from types import SimpleNamespace
+    n, T, D, cpu = 300, 60, 40, torch.device("cpu")
+    ends = list(range(T + 5, T + 5 + D))
+    dates, R, _, sec = factor_panel(max(ends) + 1, n)
+    rows, tlen = engine.window_rows(dates, dates[ends], T)
+    qb = engine.QPBatch(n, D, mg, device=cpu, shared_constraints=shared, P=torch.empty(0, dtype=torch.float64))
+    qb.P = None
+    qb.lb[:, :n], qb.ub[:, :n] = 0.0, 0.2
+    qb.lb[:, n:] = qb.ub[:, n:] = 0.0
+    if mg:
+        qb.Cg[:, 0, :n] = 1.0                       # the budget
+        qb.lg[:, 0] = qb.ug[:, 0] = 1.0
+    for r in range(1, mg):                          # 0/1 sector rows (disjoint) or dense rows
+        qb.Cg[:, r, :n] = torch.from_numpy((sec == r - 1).astype(float)) if rows_kind == "sparse" else 1.0 + r
+        qb.ug[:, r] = 0.3
+    qb.p_scale = torch.full((D,), 2.0, dtype=torch.float64)
+    if not uniform:
+        qb.p_scale[1::2] = 4.0
+    mu = torch.zeros((D, qb.ld), dtype=torch.float64) if centred else None
+    lr = SimpleNamespace(tmax=T, panel=SimpleNamespace(R=torch.from_numpy(R)), mu=mu, w_scale=None)
+    gp = engine.GroupPlan(rows, tlen, cpu, cus=cus)
+    ws = engine.Workspace(qb, dense=False)
+    assert gp.ok and engine.lowrank_applicable(qb, lr) and engine.grouped_applicable(qb, lr, gp, ws)
+    return qb, lr, gp, ws
+
+
+def _route(qb, lr, gp, ws, settings=None, **kw):
+    return engine.lowrank_route(qb, lr, ws, gp, settings or engine.Settings(), **kw)
+
+
+def _route_fields(r):
+    return (r.capacitance, r.admm, r.polish, r.band, r.loose_eps, r.loose_min_iter, r.sync_free)
+
+
+def test_lowrank_route_table():
+    """The whole route of solve_lowrank for each combination of caller flags and problem facts
+    the host code distinguishes (expected values: the conditions of the code before the route
+    was made explicit, the same the "which kernel ran" assertions of tests/test_gcap_gpu.py,
+    tests/test_admm_iterates_gpu.py and tests/test_sweep_admm_gpu.py pin on the device)."""
+    d = engine.Settings()
+    assert (d.eps_grouped, d.min_iter_grouped) == (0.5, 7)
+    # 1. defaults: the group capacitance on its own plan (20-date groups), grouped polish, the loose stop
+    #    for centred windows, sync_free honoured
+    qb, lr, gp, ws = _route_problem(cus=1)
+    assert (gp.ngroups, gp.ucnt_max, gp.corr_max) == (3, 73, 14) and gp.sizes.tolist() == [14, 14, 12]
+    g32 = gp.gcap_plan()
+    assert g32 is not gp and g32.sizes.tolist() == [20, 20]
+    r = _route(qb, lr, gp, ws)
+    assert r.grouped and r.plan is g32 and r.band_wmin == max(g32.span_max, gp.span_max) == 60 + 19
+    assert _route_fields(r) == ("group", "gcap", "grouped", True, 0.5, 7, False)
+    assert _route(qb, lr, gp, ws, sync_free=True).sync_free
+    #    uncentred (tracking) windows keep eps_abs / eps_rel
+    qb_u, lr_u, gp_u, ws_u = _route_problem(centred=False)
+    assert (gp_u.ngroups, gp_u.ucnt_max, gp_u.corr_max) == (10, 63, 4) and gp_u.gcap_plan() is gp_u
+    assert _route_fields(_route(qb_u, lr_u, gp_u, ws_u)) == ("group", "gcap", "grouped", True, 0.0, 0, False)
+    # 2. gcap=False: the grouped kernel's fused form on the band capacitance; no loose stop
+    #    (eps_grouped_percap is off), a sync_free request is refused
+    r = _route(qb, lr, gp, ws, gcap=False, sync_free=True)
+    assert r.plan is gp and r.band_wmin == gp.span_max   # (wide_polish: the polish plan's unions)
+    assert _route_fields(r) == ("band", "grouped-fused", "grouped", True, 0.0, 0, False)
+    r = _route(qb, lr, gp, ws, engine.Settings(eps_grouped_percap=True), gcap=False)
+    assert (r.admm, r.loose_eps, r.loose_min_iter) == ("grouped-fused", 0.5, 7)
+    assert _route(qb, lr, gp, ws, gcap=False, wide_polish=False).band_wmin == 0
+    # 3. fuse=False: the unfused grouped kernel, no group capacitance
+    r = _route(qb, lr, gp, ws, fuse=False, sync_free=True)
+    assert r.plan is gp and _route_fields(r) == ("band", "grouped-unfused", "grouped", True, 0.0, 0, False)
+    # 4. groups=None: the per-problem ADMM and the per-date polish
+    r = _route(qb, lr, None, ws, sync_free=True)
+    assert not r.grouped and r.plan is None and r.band_wmin == 0
+    assert _route_fields(r) == ("band", "per-problem", "per-date", True, 0.0, 0, False)
+    #    ... the per-date polish also without the grouped polish, on the group capacitance
+    assert _route_fields(_route(qb, lr, gp, ws, grouped_polish=False, sync_free=True)) == \
+        ("group", "gcap", "per-date", True, 0.0, 0, False)
+    # 5. per-problem constraints: the direct capacitance, no band, no gcap, no fused form
+    qb5, lr5, gp5, ws5 = _route_problem(shared=False)
+    r = _route(qb5, lr5, gp5, ws5, sync_free=True)
+    assert r.plan is gp5 and _route_fields(r) == ("direct", "grouped-unfused", "grouped", False, 0.0, 0, False)
+    assert _route_fields(_route(qb, lr, gp, ws, band=False)) == ("direct", "grouped-unfused", "grouped", False, 0.0, 0,
+                                                                  False)
+    # 6. the dates of a group differ in c = p_scale w_scale (a risk-aversion sweep) and a
+    #    SweepPlan is given: the sweep kernel on the band capacitance, no group capacitance
+    qb6, lr6, gp6, ws6 = _route_problem(uniform=False)
+    sp = engine.SweepPlan([4] * 10, qb6.device, q_shared=True)
+    r = _route(qb6, lr6, gp6, ws6, sweep=sp, sync_free=True)
+    assert r.plan is gp6 and _route_fields(r) == ("band", "sweep", "grouped", True, 0.0, 0, False)
+    assert _route(qb6, lr6, gp6, ws6).admm == "grouped-fused"            # (no SweepPlan)
+    assert _route(qb, lr, gp, ws, sweep=sp).admm == "gcap"               # (uniform groups: gcap wins)
+    assert _route(qb6, lr6, gp6, ws6, sweep=sp, fuse=False).admm == "grouped-unfused"
+    old = engine.SWEEP_ADMM
+    try:
+        engine.SWEEP_ADMM = False
+        assert _route(qb6, lr6, gp6, ws6, sweep=sp).admm == "grouped-fused"
+    finally:
+        engine.SWEEP_ADMM = old
+    # 7. as 6 with the per-date eigendecompositions: "eig", the sweep kernel still chosen
+    r = _route(qb6, lr6, gp6, ws6, sweep=sp, eig=object())
+    assert _route_fields(r) == ("eig", "sweep", "grouped", True, 0.0, 0, False)
+    assert _route(qb, lr, gp, ws, eig=object()).admm == "grouped-fused"  # (eig: never the group capacitance)
+    # 8. more than 4 general rows: gcap only in the column-sparse form (budget + 8 disjoint 0/1 rows)
+    qb8, lr8, gp8, ws8 = _route_problem(mg=9)
+    r = _route(qb8, lr8, gp8, ws8)
+    assert r.sparse_cols[2] == 2 and _route_fields(r) == ("group", "gcap", "grouped", True, 0.5, 7, False)
+    qb8u, lr8u, gp8u, ws8u = _route_problem(mg=9, centred=False)       # tracking, wide form: its own loose stop
+    assert d.eps_grouped_tracking_wide == 1e-2
+    assert _route_fields(_route(qb8u, lr8u, gp8u, ws8u)) == ("group", "gcap", "grouped", True, 1e-2, 7, False)
+    qb8d, lr8d, gp8d, ws8d = _route_problem(mg=5, rows_kind="dense")
+    r = _route(qb8d, lr8d, gp8d, ws8d)
+    assert r.sparse_cols[2] == 0 and _route_fields(r) == ("band", "grouped-fused", "grouped", True, 0.0, 0, False)
+    # 9. polish=False (or settings.polish = 0): no polish, no loose stop, sync_free refused
+    for kw in (dict(polish=False), dict(settings=engine.Settings(polish=0))):
+        r = _route(qb, lr, gp, ws, sync_free=True, **kw)
+        assert r.plan is g32 and _route_fields(r) == ("group", "gcap", "none", True, 0.0, 0, False)
+    # 10. engine.GCAP_MAX_DATES = 16 (read when the plan is first asked for): the plan is groups itself
+    qb10, lr10, gp10, ws10 = _route_problem(cus=1)
+    old = engine.GCAP_MAX_DATES
+    try:
+        engine.GCAP_MAX_DATES = 16
+        r = _route(qb10, lr10, gp10, ws10)
+    finally:
+        engine.GCAP_MAX_DATES = old
+    assert r.plan is gp10 and _route_fields(r) == ("group", "gcap", "grouped", True, 0.5, 7, False)
+    #     ... and engine.GCAP32_WIDE = False keeps the 16-date groups for the column-sparse form only
+    qbw, lrw, gpw, wsw = _route_problem(mg=9, cus=1)
+    old = engine.GCAP32_WIDE
+    try:
+        engine.GCAP32_WIDE = False
+        assert _route(qbw, lrw, gpw, wsw).plan is gpw and _route(qb, lr, gp, ws).plan is g32
+    finally:
+        engine.GCAP32_WIDE = old
+    assert _route(qbw, lrw, gpw, wsw).plan is gpw.gcap_plan() is not gpw
+
+
+def test_workspace_declares_what_the_engine_sets():
+    """Every attribute solve_lowrank later sets exists (None) on a new Workspace."""
+    qb, _, _, ws = _route_problem()
+    for name in ("sweep_admm", "band_shape", "gcap_groups", "pg_fallback", "_pg_pass", "_sf_flag", "_pg_rec",
+                 "_gcap", "_pgw"):
+        assert name in vars(ws) and getattr(ws, name) is None, name
