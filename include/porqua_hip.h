@@ -237,6 +237,16 @@ int pq_init_state_lr(const pq_lowrank* lr, const pq_problem* pb, pq_state* st, c
 int pq_factor_batched(const pq_problem* pb, pq_state* st, const int32_t* idx, int32_t nidx,
                       const pq_settings* s, int32_t invert, void* stream);
 
+/* The kernel the calling thread's last pq_factor_batched launched: 0 the generic k_factor,
+ * 1 the split-K k_factor_sk, 2 the register-resident k_factor_res (an inverse of a plain
+ * matrix, mg = 0 and no box, n <= 288 at ld <= 320, few problems); -1 before any call.   */
+int pq_factor_last_route(void);
+
+/* PQ_PROFILE builds: the resident kernel's phase clocks of the last launch, 8 int64 slots per
+ * workgroup (load, potrf, trtri, lauum, store in 100 MHz ticks), nblocks <= 1024 workgroups,
+ * copied to the host array `out` (synchronises).  Other builds return -1.                 */
+int pq_factor_res_prof(long long* out, int32_t nblocks);
+
 /* K2L: pq_factor_batched for LARGE problems (the per-QP drop-in at thousands of assets:
  * QuadraticProgram.solve with a dense n x n P, src/qp_problems.py:184-216, called per date by
  * the serial Backtest.run, src/backtest.py:185-199).  Same K formation, info[] / status and

@@ -159,6 +159,8 @@ _EXPORTS = {
                        ctypes.POINTER(PQSettings), c_dp], c_int32),
     "pq_factor_batched": ([ctypes.POINTER(PQProblem), ctypes.POINTER(PQState), c_dp, c_int32,
                            ctypes.POINTER(PQSettings), c_int32, c_dp], c_int32),
+    "pq_factor_last_route": ([], c_int32),
+    "pq_factor_res_prof": ([c_dp, c_int32], c_int32),
     "pq_factor_large": ([ctypes.POINTER(PQProblem), ctypes.POINTER(PQState), c_dp, c_int32,
                          ctypes.POINTER(PQSettings), c_int32, c_dp, c_int64, c_dp], c_int32),
     "pq_sym_eig_work_doubles": ([c_int32], c_int64),

@@ -14,6 +14,7 @@
 // factorisation inside qpsolvers' backends (src/qp_problems.py:211-214).
 #include "chol_dev.h"
 #include "capi_util.h"
+#include "chol_res.h"
 
 namespace pq {
 
@@ -273,6 +274,11 @@ __global__ __launch_bounds__(512, 1) void k_factor_sk(pq_problem pb, pq_state st
 }
 }  // namespace pq
 
+// the kernel pq_factor_batched launched last on this host thread: 0 k_factor, 1 k_factor_sk,
+// 2 k_factor_res (-1: none yet)
+static thread_local int g_last_route = -1;
+extern "C" int pq_factor_last_route(void) { return g_last_route; }
+
 extern "C" int pq_factor_batched(const pq_problem* pb, pq_state* st, const int32_t* idx,
                                  int32_t nidx, const pq_settings* s, int32_t invert,
                                  void* stream) {
@@ -294,7 +300,23 @@ extern "C" int pq_factor_batched(const pq_problem* pb, pq_state* st, const int32
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const bool sk = sk_env >= 0 ? sk_env > 0 : (invert != 0 && grid <= cus);
-  if (sk)
+  // an inverse of a plain matrix (mg = 0, no box) of n <= 288 at pitch <= 320: the register-resident
+  // kernel (chol_res.hip), one workgroup per problem and CU.  Bound on the number of problems: measured
+  // against k_factor (two 256-thread workgroups per CU) at n = 284, ld = 320 on 256 CUs, us per launch,
+  // resident / k_factor:  256 problems 353 / 598,  384: 670 / 834,  512: 701 / 887,  1024: 1354 / 1716
+  // (profiles/r07_factor_crossover.log) -- ahead at every count measured, so the bound is the largest
+  // of them, 4 problems per CU, at that pitch; smaller pitches (not measured) keep k_factor_sk's bound of one
+  // problem per CU.  PQ_FACTOR_RES = 0 / 1 forces the choice where the form is supported (A/B)
+  static const int res_env = [] {
+    const char* e = getenv("PQ_FACTOR_RES");
+    return e ? atoi(e) : -1;
+  }();
+  const bool res = invert != 0 && pq::factor_res_supports(pb) &&
+                   (res_env >= 0 ? res_env > 0 : (sk_env < 0 && grid <= (pb->ld > 256 ? 4 * cus : cus)));
+  g_last_route = res ? 2 : (sk ? 1 : 0);
+  if (res)
+    pq::factor_res_launch(grid, (hipStream_t)stream, pb, st, idx, nidx, s, invert);
+  else if (sk)
     hipLaunchKernelGGL(pq::k_factor_sk, dim3(grid), dim3(512), 0, (hipStream_t)stream, *pb, *st, idx,
                        nidx, *s, invert);
   else
