@@ -564,6 +564,31 @@ int pq_psd_form_batched(const double* V, int64_t v_stride, const double* evals, 
 int pq_tile_gemm_batched(const double* A, int64_t sa, int32_t ta, const double* B, int64_t sb, int32_t tb,
                          double* C, int64_t sc, int32_t ld, int32_t batch, void* stream);
 
+/* Quantile portfolios of a batch of dates (PercentilePortfolios.solve,
+ * src/optimization.py:398-417): x = sign * scores[b] (sign = -1 is the reference's negation of
+ * the raw scores; row stride lds >= n, columns beyond n never read), thresholds
+ * th[b][t] = numpy's linear-interpolation percentile of x at 100 t / N, t = 0..N, from the
+ * host-computed plan (prev[t], next[t]: order-statistic indices; gamma[t]: the weight;
+ * th = a + (b - a) gamma, or b - (b - a)(1 - gamma) where gamma >= 0.5, without fused
+ * multiply-adds, so it is np.percentile bit for bit), bucket[b][j] = smallest i in 1..N with
+ * x_j <= th[i], counts[b][i-1] = members of bucket i, and the long-short weights
+ * w[b][j] = +1 / counts[0] on bucket 1, then -1 / counts[N-1] on bucket N (the second wins),
+ * 0 elsewhere.  status[b]: PQ_PCT_OK; PQ_PCT_EMPTY_BUCKET (the reference's
+ * ZeroDivisionError: ties, N > n; th / bucket / counts are written, w[b] is NaN);
+ * PQ_PCT_NAN_SCORE (a NaN among the n scores: th[b] and w[b] NaN, bucket and counts 0).  A
+ * failing row touches no other row.  th batch x (N+1), bucket and w batch x n, counts
+ * batch x N, all contiguous; one workgroup per date, an exact LDS bitonic sort of the keys.
+ * 1 <= n <= PQ_PCT_MAX_N (128 KiB of FP64 keys in LDS), 1 <= N <= PQ_PCT_MAX_BUCKETS.      */
+#define PQ_PCT_OK 0
+#define PQ_PCT_EMPTY_BUCKET 1
+#define PQ_PCT_NAN_SCORE 2
+#define PQ_PCT_MAX_N 16384
+#define PQ_PCT_MAX_BUCKETS 256
+int pq_percentile_batched(const double* scores, int64_t lds, int32_t n, int32_t batch, double sign,
+                          int32_t n_percentiles, const int32_t* prev, const int32_t* next,
+                          const double* gamma, double* th, int32_t* bucket, int32_t* counts, double* w,
+                          int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

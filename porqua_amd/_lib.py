@@ -25,6 +25,11 @@ PQ_PRIMAL_INFEASIBLE = -3
 PQ_DUAL_INFEASIBLE = -4
 PQ_NON_CONVEX = -5
 
+# pq_percentile_batched: per-date status and the supported range (include/porqua_hip.h)
+PQ_PCT_OK, PQ_PCT_EMPTY_BUCKET, PQ_PCT_NAN_SCORE = range(3)
+PQ_PCT_MAX_N = 16384
+PQ_PCT_MAX_BUCKETS = 256
+
 PQ_PG_RECORD = 384                   # doubles per problem of the grouped polish record
 PQ_PG_PASS_SCRATCH = 123537          # doubles per slide group of the split polish window passes
 PQ_PG_PENDING, PQ_PG_DONE, PQ_PG_FALLBACK, PQ_PG_SKIP = range(4)
@@ -219,6 +224,8 @@ _EXPORTS = {
                            c_dp, c_int64, c_dp], c_int32),
     "pq_wgram_batched": ([c_dp, c_int64, c_int64, c_int32, c_int32, c_int32, c_dp, c_int64, c_dp, c_int64,
                           c_dp, c_int64, c_dp, c_int32, c_int64, c_dp], c_int32),
+    "pq_percentile_batched": ([c_dp, c_int64, c_int32, c_int32, ctypes.c_double, c_int32, c_dp, c_dp, c_dp,
+                               c_dp, c_dp, c_dp, c_dp, c_dp, c_dp], c_int32),
 }
 
 _lib = None

@@ -18,6 +18,9 @@ loop runs in two phases instead of one serial QP per date:
     the weight panel -- SURVEY.md §8(e));
   C (host): Portfolio objects in date order, ``append_fun`` called per date.
 
+PercentilePortfolios (no QP) batches the same way: phase A, then the scores of every date
+from the device geometric means and one ranking launch (``_run_percentile``).
+
 Dates are independent in the reference; an ``append_fun`` that mutates
 state read by later dates is not supported in batched mode (set settings['batched'] = False
 to force the serial loop, which still solves each date on the device).
@@ -267,6 +270,31 @@ class _PanelUpload:
         return self._out
 
 
+def _stage_windows(bs, universe, rebdates):
+    """The selected return frame, its panel upload (started here) and the window row lists of
+    every rebalance date: (Xs, upload, index, rows, tlen), or None without a
+    bibfn_return_series width."""
+    from . import engine
+    X = bs.data.get("return_series")
+    if X is None:
+        raise ValueError("Return series data is missing.")
+    width = None
+    for bld in bs.optimization_item_builders.values():
+        if bld.arguments.get("bibfn") is _b.bibfn_return_series:
+            width = bld.arguments.get("width")
+    if width is None:
+        return None
+    # the whole frame when the selection is every column in order (no 8 T n-byte copy)
+    Xs = X if list(X.columns) == list(universe) else X[universe]
+    # the panel upload (D x n FP64 over PCIe) runs on a worker thread while this thread
+    # builds the window and group plans (the copy releases the GIL); the solve joins it
+    upload = _PanelUpload(Xs)
+    idx = pd.DatetimeIndex(Xs.index)
+    dates = idx.values.astype("datetime64[D]")
+    rows, tlen = engine.window_rows(dates, np.array(rebdates, dtype="datetime64[D]"), width)
+    return Xs, upload, idx, rows, tlen
+
+
 def _batchable(bs) -> bool:
     """Batched mode needs builders whose output does not depend on the date beyond the
     return / benchmark windows: the standard ones, or any set the caller declares
@@ -317,7 +345,11 @@ class Backtest:
 
     def run(self, bs: BacktestService) -> None:
         from .qp_problems import ENGINE_SOLVERS
-        if bs.optimization.params.get("solver_name") in ENGINE_SOLVERS and _batchable(bs):
+        if hasattr(bs.optimization, "percentile_batch") and _batchable(bs):
+            # quantile portfolios: no QP, so no engine solver name; every date ranked in one launch
+            if self._run_percentile(bs):
+                return None
+        elif bs.optimization.params.get("solver_name") in ENGINE_SOLVERS and _batchable(bs):
             if self._run_batched(bs):
                 return None
         return self._run_serial(bs)
@@ -369,7 +401,6 @@ class Backtest:
         """Phase A (host, once): selection and constraints of the first date (date-invariant
         builders), window row lists of every rebalance date, benchmark alignment, G/h/A/b and
         the box.  Returns the staging dict, or None when the run cannot batch."""
-        from . import engine
         rebdates = list(bs.settings["rebdates"])
         if not rebdates:
             return None
@@ -387,23 +418,10 @@ class Backtest:
             if l1both is None:
                 return None
             l1term = None
-        X = bs.data.get("return_series")
-        if X is None:
-            raise ValueError("Return series data is missing.")
-        width = None
-        for bld in bs.optimization_item_builders.values():
-            if bld.arguments.get("bibfn") is _b.bibfn_return_series:
-                width = bld.arguments.get("width")
-        if width is None:
+        ws = _stage_windows(bs, universe, rebdates)
+        if ws is None:
             return None
-        # the whole frame when the selection is every column in order (no 8 T n-byte copy)
-        Xs = X if list(X.columns) == list(universe) else X[universe]
-        # the panel upload (D x n FP64 over PCIe) runs on a worker thread while this thread
-        # builds the window and group plans (the copy releases the GIL); _solve_shard joins it
-        upload = _PanelUpload(Xs)
-        idx = pd.DatetimeIndex(Xs.index)
-        dates = idx.values.astype("datetime64[D]")
-        rows, tlen = engine.window_rows(dates, np.array(rebdates, dtype="datetime64[D]"), width)
+        Xs, upload, idx, rows, tlen = ws
         bm = None
         ys = bs.data.get("bm_series")
         if ys is not None:
@@ -641,6 +659,60 @@ class Backtest:
             last = len(rebdates) - 1
             w = W[last].tolist() if solved[last] else none
             opt.results = {"weights": dict(zip(keys, w)), "status": bool(solved[last])}
+
+    def _run_percentile(self, bs) -> bool:
+        """Batched run of PercentilePortfolios (estimator form): phase A as for the QP path
+        (static selection, panel upload, window rows), then the scores of every date from the
+        device geometric means and one ranking launch (``percentile_batch``), one copy of the
+        weights and bucket ids to the host, and phase C.  The constraints the builders add are
+        ignored, as in the reference.  False: the serial loop has to run (a custom score
+        frame, missing values in the panel, an empty estimator window).
+
+        Under an initialised process group every rank computes all dates and no collective
+        runs: the whole job is O(dates x assets), less than one all-gather's latency."""
+        from . import _lib, engine
+        from .optimization import percentile_results
+        rebdates = list(bs.settings["rebdates"])
+        if not rebdates:
+            return False
+        opt = bs.optimization
+        bs.prepare_rebalancing(rebalancing_date=rebdates[0])
+        universe = bs.selection.selected
+        ws = _stage_windows(bs, universe, rebdates)
+        if ws is None:
+            return False
+        _, upload, _, rows, tlen = ws
+        dev = engine.default_device()
+        panel = engine.Panel(upload.result(), None, device=dev)
+        if panel.has_nan:
+            return False
+        out = opt.percentile_batch(BatchStage(panel, rows, tlen, dev))
+        if out is None:
+            return False
+        # the weight panel lands in page-locked host memory, as on the QP path (the lazy
+        # Portfolio objects keep views of its rows)
+        Wt, W = _pinned_panel(len(rebdates), len(universe))
+        Wt.copy_(out[0])
+        bucket, counts, status = (t.cpu().numpy() for t in (out[1], out[2], out[4]))
+        bad = np.flatnonzero(status != _lib.PQ_PCT_OK)
+        if bad.size:   # the reference's ZeroDivisionError, re-raised by rebalance() as RuntimeError
+            what = "a NaN score" if status[bad[0]] == _lib.PQ_PCT_NAN_SCORE else "an empty percentile bucket"
+            raise RuntimeError(f"division by zero: {what} at rebalancing date {rebdates[bad[0]]}")
+        self.stats = {"dates": len(rebdates), "solved": len(rebdates), "status": status, "path": "percentile",
+                      "bucket": bucket, "counts": counts}
+        if not bs.settings.get("quiet"):
+            print(f"Ranked {len(rebdates)} dates on the device")
+        keys = list(universe)
+        index = pd.Index(keys)
+        if bs.settings.get("append_fun") is None:
+            self.strategy.portfolios.extend(Portfolio._from_row(d, keys, W[i]) for i, d in enumerate(rebdates))
+        else:
+            for i, d in enumerate(rebdates):
+                opt.results = percentile_results(index, W[i], bucket[i], counts[i])
+                self._after_solve(bs, d)
+        # the optimisation's results hold the last date's, as after the serial loop
+        opt.results = percentile_results(index, W[-1], bucket[-1], counts[-1])
+        return True
 
     def save(self, filename: str, path: Optional[str] = None) -> None:
         try:

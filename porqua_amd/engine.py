@@ -1813,3 +1813,69 @@ def simulate_periods(panel: torch.Tensor, W: torch.Tensor, plan, nrows=None, ret
         _ptr(plan.off), _ptr(plan.ret_day), float(fc), float(days_per_year), _ptr(ret), _ptr(wend),
         n, _ptr(to), int(bool(rescale)), _stream()), "pq_simulate_periods")
     return ret[:total], wend, (to[:nper] if to is not None else None)
+
+
+# ----------------------------------------------------------------------------------------
+# Quantile portfolios (PercentilePortfolios, src/optimization.py:356-417)
+# ----------------------------------------------------------------------------------------
+
+_PCT_PLANS: dict = {}
+
+
+def percentile_plan(n: int, n_percentiles: int):
+    """np.percentile's index plan for n values at linspace(0, 100, N + 1), with numpy's own
+    arithmetic (numpy/lib/_function_base_impl.py: percentile, _quantile, _get_indexes,
+    _get_gamma; method 'linear'): (prev int32 [N+1], next int32 [N+1], gamma float64 [N+1]).
+    Threshold t interpolates the order statistics prev[t] and next[t] with weight gamma[t]."""
+    n, N = int(n), int(n_percentiles)
+    q = np.true_divide(np.linspace(0, 100, N + 1), np.float64(100))
+    v = (n - 1) * q                               # virtual index
+    prev = np.floor(v)
+    nxt = prev + 1
+    above = v >= n - 1                            # at the maximum: both indices are -1 (the last)
+    prev[above] = -1
+    nxt[above] = -1
+    gamma = v - prev                              # _get_gamma sees the -1 (the two values are equal there)
+    prev = prev.astype(np.intp) % n
+    nxt = nxt.astype(np.intp) % n
+    return prev.astype(np.int32), nxt.astype(np.int32), gamma.astype(np.float64)
+
+
+def percentile_weights(scores: torch.Tensor, n_percentiles: int, sign: float = -1.0, n: int | None = None):
+    """Quantile portfolios of every row of a device score panel (pq_percentile_batched;
+    PercentilePortfolios.solve, src/optimization.py:398-417).  ``scores`` is an FP64 device
+    tensor (B, n), or (B, ld) with ``n`` given (columns beyond n are never read); ``sign`` = -1
+    ranks the raw scores as the reference does (its objective holds -scores).  Returns
+    (w [B, n] long-short weights, bucket [B, n] int32 in 1..N, counts [B, N] int32,
+    th [B, N+1] thresholds of sign * scores, status [B] int32: _lib.PQ_PCT_*), all on the
+    device.  A row with an empty bucket or a NaN score has a non-OK status and NaN weights."""
+    if scores.dim() != 2 or scores.dtype != F64 or not scores.is_cuda:
+        raise ValueError("percentile_weights: FP64 device tensor (B, n) expected")
+    B = int(scores.shape[0])
+    n = int(scores.shape[1]) if n is None else int(n)
+    N = int(n_percentiles)
+    if not 1 <= n <= min(_lib.PQ_PCT_MAX_N, int(scores.shape[1])):
+        raise ValueError(f"percentile_weights: n = {n} outside 1..{_lib.PQ_PCT_MAX_N} (the keys of one date are "
+                         "sorted in LDS) or beyond the panel's columns")
+    if not 1 <= N <= _lib.PQ_PCT_MAX_BUCKETS:
+        raise ValueError(f"percentile_weights: n_percentiles = {N} outside 1..{_lib.PQ_PCT_MAX_BUCKETS}")
+    if float(sign) not in (1.0, -1.0):
+        raise ValueError("percentile_weights: sign must be +1 or -1")
+    if scores.stride(1) != 1 or (B > 1 and scores.stride(0) < n):
+        scores = scores.contiguous()
+    lds = max(int(scores.stride(0)), n)           # (a one-row tensor may report any row stride)
+    dev = scores.device
+    plan = _PCT_PLANS.get((n, N, dev))
+    if plan is None:
+        plan = tuple(torch.from_numpy(a).to(dev) for a in percentile_plan(n, N))
+        _PCT_PLANS[(n, N, dev)] = plan
+    w = torch.empty((B, n), dtype=F64, device=dev)
+    bucket = torch.empty((B, n), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, N), dtype=torch.int32, device=dev)
+    th = torch.empty((B, N + 1), dtype=F64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    if B:
+        _lib.check(_lib.load().pq_percentile_batched(
+            _ptr(scores), lds, n, B, float(sign), N, _ptr(plan[0]), _ptr(plan[1]), _ptr(plan[2]),
+            _ptr(th), _ptr(bucket), _ptr(counts), _ptr(w), _ptr(status), _stream()), "pq_percentile_batched")
+    return w, bucket, counts, th, status

@@ -3,7 +3,7 @@
 # Minh Ha Ho and licensed under the GNU LGPL v3; this module keeps that API and its
 # behaviour (quirks included) so that the MI355X engine is a drop-in, and is distributed
 # under the same licence terms.
-"""PD test / repair and small helpers (mirror of src/helper_functions.py:29-83).
+"""PD test / repair and small helpers (mirror of src/helper_functions.py:29-99).
 
 ``isPD`` is the batched device Cholesky (K2) info flag.  ``nearestPD`` is the reference's
 Higham / D'Errico repair (src/helper_functions.py:29-58) on the device for a whole batch,
@@ -32,6 +32,23 @@ F64 = torch.float64
 def to_numpy(data):
     """src/helper_functions.py:82-83."""
     return None if data is None else data.to_numpy() if hasattr(data, "to_numpy") else data
+
+
+def output_to_strategies(output: dict) -> dict:
+    """src/helper_functions.py:86-99: the ``weights_1 .. weights_N`` entries that
+    ``append_custom`` stored per rebalancing date (``Backtest.output``) as one Strategy per
+    quantile, {'q1': Strategy, ..., 'qN': Strategy}."""
+    from .portfolio import Portfolio, Strategy
+    N = len(output[list(output.keys())[0]])
+    strategy_dict = {}
+    for i in range(N):
+        strategy_dict[f"q{i + 1}"] = Strategy([])
+        for rebdate in output.keys():
+            weights = output[rebdate][f"weights_{i + 1}"]
+            if hasattr(weights, "to_dict"):
+                weights = weights.to_dict()
+            strategy_dict[f"q{i + 1}"].portfolios.append(Portfolio(rebdate, weights))
+    return strategy_dict
 
 
 def _as_batch(A):

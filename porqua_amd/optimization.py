@@ -15,8 +15,11 @@ Deliberate differences from the reference ("Reference defects"):
   package) and lets ``verbose=False`` stick (src/optimization.py:45-46).
 * ``MeanVariance`` uses the mean estimator that is passed in; the reference stores the
   class instead of the instance (src/optimization.py:165).
-LAD runs on the batched device IPM of porqua_amd/lad.py; PercentilePortfolios (ranking,
-not the QP path) is not built.
+* ``PercentilePortfolios`` leaves out the reference's unseeded noise on exact-zero scores
+  (src/optimization.py:393); zero weights are +0.0.
+LAD runs on the batched device IPM of porqua_amd/lad.py; PercentilePortfolios (ranking, not
+the QP path) runs on the batched order-statistics kernel (pq_percentile_batched), one date
+in ``solve()`` and every date of a backtest through ``percentile_batch``.
 """
 from __future__ import annotations
 
@@ -451,3 +454,107 @@ class LAD(Optimization):
                                                   q=np.append(np.zeros(N), np.ones(2 * T)),
                                                   G=G_t, h=GhAb["h"], A=A_t, b=b_t, lb=lb, ub=ub,
                                                   params=self.params)
+
+
+class PercentilePortfolios(Optimization):
+    """Quantile portfolios by score rank (src/optimization.py:356-417): the assets are cut
+    into ``n_percentiles`` buckets at np.percentile thresholds of the negated scores;
+    ``results['w_dict'][i]`` holds bucket i equally weighted, ``results['weights']`` the
+    long-short portfolio bucket 1 minus bucket N.  The ranking runs on the device
+    (engine.percentile_weights); ``percentile_batch`` ranks every date of a backtest at once.
+
+    As in the reference, ``params`` becomes a plain dict {'solver_name', 'n_percentiles',
+    'field'} (so any other keyword, the walkthrough's misspelt ``n_percentile`` included, is
+    ignored), and the constraints the builders add are not used.  The reference's unseeded
+    noise on exact-zero scores (src/optimization.py:393) is not reproduced: zeros tie like
+    any equal scores."""
+
+    def __init__(self, field: Optional[str] = None, estimator: Optional[MeanEstimator] = None,
+                 n_percentiles=5, **kwargs):
+        super().__init__(**kwargs)
+        self.estimator = estimator
+        self.params = {"solver_name": "percentile", "n_percentiles": n_percentiles, "field": field}
+
+    def set_objective(self, optimization_data: OptimizationData) -> None:
+        field = self.params.get("field")
+        if self.estimator is not None:
+            if field is not None:
+                raise ValueError('Either specify a "field" or pass an "estimator", but not both.')
+            scores = self.estimator.estimate(X=optimization_data["return_series"])
+        elif field is not None:
+            scores = optimization_data["scores"][field]
+        else:
+            score_weights = self.params.get("score_weights")
+            if score_weights is not None:
+                scores = (optimization_data["scores"][score_weights.keys()]
+                          .multiply(score_weights.values()).sum(axis=1))
+            else:
+                scores = optimization_data["scores"].mean(axis=1).squeeze()
+        self.objective = Objective(scores=-scores)
+
+    def solve(self) -> bool:
+        """src/optimization.py:398-417 on the device at batch 1.  An empty bucket (or a NaN
+        score, which empties every bucket there) is the reference's ZeroDivisionError."""
+        import torch
+        from . import _lib, engine
+        scores = self.objective["scores"]
+        N = self.params["n_percentiles"]
+        index = scores.index if hasattr(scores, "index") else pd.RangeIndex(len(scores))
+        x = np.ascontiguousarray(to_numpy(scores), dtype=np.float64).reshape(1, -1)
+        # the objective already holds -scores: the kernel ranks it as it is (sign +1)
+        w, bucket, counts, _th, status = engine.percentile_weights(
+            torch.from_numpy(x).to(engine.default_device()), N, sign=1.0)
+        if int(status[0].item()) != _lib.PQ_PCT_OK:
+            raise ZeroDivisionError("division by zero")
+        self.results = percentile_results(index, w[0].cpu().numpy(), bucket[0].cpu().numpy(),
+                                          counts[0].cpu().numpy())
+        return True
+
+    def percentile_batch(self, stage):
+        """Every date of a backtest chunk in one launch: the device geometric means over each
+        date's own estimator sub-window (MeanEstimator.window of that date's window length, so
+        ragged early windows batch too), then engine.percentile_weights on the raw scores
+        (sign -1).  Returns (w, bucket, counts, th, status) on the device, or None when the
+        run has to take the serial loop (the ``field`` / ``scores`` forms, another estimator,
+        a window the estimator leaves empty)."""
+        import torch
+        from . import engine
+        me = self.estimator
+        if me is None or self.params.get("field") is not None or me.spec.get("method") != "geometric":
+            return None
+        t = stage.tlen_host.astype(np.int64)
+        if len(t) == 0:
+            return None
+        win = {int(v): me.window(int(v)) for v in np.unique(t)}
+        a = np.array([win[int(v)][0] for v in t], dtype=np.int64)
+        L = np.array([win[int(v)][1] for v in t], dtype=np.int64) - a
+        if L.min() < 1:
+            return None
+        if not a.any() and np.array_equal(L, t):      # the whole window of every date
+            gp = stage.group_plan()
+            if gp.ok:   # slide groups: one sliding log-sum pass per group
+                mu = stage.panel.window_geomeans_grouped(gp, stage.tlen)
+            else:
+                mu = stage.panel.window_means(stage.rows, stage.tlen, geometric=True)
+        else:
+            j = np.arange(int(L.max()), dtype=np.int64)[None, :]
+            pos = np.minimum(a[:, None] + j, stage.rows_host.shape[1] - 1)
+            mrows = np.take_along_axis(stage.rows_host, pos, axis=1) * (j < L[:, None])
+            mrows, mtlen = stage.panel.rows_to_device(mrows, L)
+            mu = stage.panel.window_means(mrows, mtlen, geometric=True)
+        sf = me.spec.get("scalefactor")
+        if sf not in (None, 1):
+            mu = torch.expm1(torch.log1p(mu) * sf)
+        return engine.percentile_weights(mu, self.params["n_percentiles"], sign=-1.0, n=stage.n)
+
+
+def percentile_results(index, w, bucket, counts) -> dict:
+    """``PercentilePortfolios.results`` of one date with the reference's types
+    (src/optimization.py:411-416): 'weights' a dict over the universe, 'w_dict' {i: Series over
+    bucket i's members in universe order, each 1 / len(bucket i)}."""
+    index = index if isinstance(index, pd.Index) else pd.Index(index)
+    w_dict = {}
+    for i in range(1, len(counts) + 1):
+        members = np.flatnonzero(bucket == i)
+        w_dict[i] = pd.Series(np.full(len(members), 1 / int(counts[i - 1])), index=index[members])
+    return {"weights": dict(zip(index, w.tolist())), "w_dict": w_dict}
