@@ -34,7 +34,9 @@ extern "C" {
 #define PQ_DUAL_INFEASIBLE (-4)
 #define PQ_NON_CONVEX (-5)      /* KKT Cholesky failed                                   */
 
-/* per-problem output record (pq_state.out, PQ_OUT_FIELDS doubles each) */
+/* per-problem output record (pq_state.out, PQ_OUT_FIELDS doubles each).  pq_init_state(_lr) sets
+ * OBJ, PRIM, DUAL and GAP to NaN and the rest to 0; the polish kernel that scores the point
+ * overwrites them, so a record without a polish does not read as a perfect one.            */
 #define PQ_OUT_OBJ 0        /* 0.5 x'Px + q'x (no constant; test:72,82)               */
 #define PQ_OUT_PRIM 1       /* qpsolvers primal_residual()                              */
 #define PQ_OUT_DUAL 2       /* qpsolvers dual_residual()                                */

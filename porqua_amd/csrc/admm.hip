@@ -592,7 +592,11 @@ __global__ void k_init_state(pq_problem pb, pq_state st, const int32_t* idx, pq_
     st.iters[b] = 0;
     st.status[b] = PQ_UNSOLVED;
     st.info[b] = 0;
-    for (int k = 0; k < PQ_OUT_FIELDS; ++k) st.out[(int64_t)b * PQ_OUT_FIELDS + k] = 0.0;
+    // nothing has scored the point yet: objective, residuals and gap are NaN until a polish kernel
+    // writes them (an unscored record must not read as a perfect one: max(NaN, ...) <= eps is false)
+    for (int k = 0; k < PQ_OUT_FIELDS; ++k)
+      st.out[(int64_t)b * PQ_OUT_FIELDS + k] = (k == PQ_OUT_OBJ || k == PQ_OUT_PRIM || k == PQ_OUT_DUAL ||
+                                                k == PQ_OUT_GAP) ? __builtin_nan("") : 0.0;
   }
 }
 

@@ -381,7 +381,7 @@ __global__ __launch_bounds__(PT) void k_polish(pq_problem pb, pq_state st, const
       if (lg[r] == ug[r]) v = fabs(sum - ug[r]);
       else v = fmax(isinf(ug[r]) ? 0.0 : sum - ug[r], isinf(lg[r]) ? 0.0 : lg[r] - sum);
       part[r] = v;
-      part[64 + r] = (lam > 0.0 ? ug[r] : (isinf(lg[r]) ? 0.0 : lg[r])) * lam;
+      part[64 + r] = (lam > 0.0 ? (isinf(ug[r]) ? 0.0 : ug[r]) : (isinf(lg[r]) ? 0.0 : lg[r])) * lam;
       sy[r] = lam;
       sz[r] = sum;
     }

@@ -2335,7 +2335,7 @@ __global__ __launch_bounds__(PPT) void k_pg_post(pq_lowrank lr, pq_problem pb, p
     else v = fmax(isinf(ug[r]) ? 0.0 : sum - ug[r], isinf(lg[r]) ? 0.0 : lg[r] - sum);
     if (hl == 0) {
       pres = fmax(pres, v);
-      gapb += (lam > 0.0 ? ug[r] : (isinf(lg[r]) ? 0.0 : lg[r])) * lam;
+      gapb += (lam > 0.0 ? (isinf(ug[r]) ? 0.0 : ug[r]) : (isinf(lg[r]) ? 0.0 : lg[r])) * lam;
       sy[r] = lam;
       sz[r] = sum;
     }

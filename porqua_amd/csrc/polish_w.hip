@@ -824,7 +824,7 @@ __global__ __launch_bounds__(PT) void k_polish_w(pq_lowrank lr, pq_problem pb, p
       if (lg[r] == ug[r]) v = fabs(sum - ug[r]);
       else v = fmax(isinf(ug[r]) ? 0.0 : sum - ug[r], isinf(lg[r]) ? 0.0 : lg[r] - sum);
       part[r] = v;
-      part[64 + r] = (lam > 0.0 ? ug[r] : (isinf(lg[r]) ? 0.0 : lg[r])) * lam;
+      part[64 + r] = (lam > 0.0 ? (isinf(ug[r]) ? 0.0 : ug[r]) : (isinf(lg[r]) ? 0.0 : lg[r])) * lam;
       sy[r] = lam;
       sz[r] = sum;
     }

@@ -398,7 +398,11 @@ class BatchResult:
     z_box: torch.Tensor      # (B, n)
     status: torch.Tensor     # (B,) int32
     iters: torch.Tensor      # (B,) int32
-    out: torch.Tensor        # (B, PQ_OUT_FIELDS)
+    # (B, PQ_OUT_FIELDS): the certificate of the returned point, written by the polish kernel that
+    # scored it -- OBJ, PRIM, DUAL, GAP (qpsolvers' definitions, of exactly the x, y, z_box above),
+    # RHO, NFREE, ROUNDS.  With the polish off (Settings.polish = 0 / polish=False) nothing scores
+    # the ADMM point and OBJ, PRIM, DUAL, GAP are NaN: an unscored point is not a certified one
+    out: torch.Tensor
     refactors: int = 0
     admm_launches: int = 0
     polish_fallbacks: int = 0   # dates the grouped polish handed to the per-date kernel

@@ -6,6 +6,11 @@ PorQua reads ``solution.found`` and ``solution.x`` (src/optimization.py:80-87), 
 ``dual_residual()`` and ``duality_gap()`` (src/helper_functions.py:69-80).  The residual
 definitions are those of qpsolvers >= 3 as quoted in example/compare_solver.ipynb:212-216.
 Values are computed on the device by the polish kernel (K4); this class only holds them.
+They are the residuals of exactly the returned ``x``, ``y``, ``z``, ``z_box``
+(tests/test_out_record_gpu.py pins them to an extended-precision model).  A point nothing has
+scored -- an engine solve with the polish switched off -- carries NaN in ``obj``,
+``primal_residual()``, ``dual_residual()`` and ``duality_gap()``: ``found`` may be true,
+``is_optimal()`` is false.
 """
 from __future__ import annotations
 
