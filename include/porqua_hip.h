@@ -591,6 +591,28 @@ int pq_percentile_batched(const double* scores, int64_t lds, int32_t n, int32_t 
                           const double* gamma, double* th, int32_t* bucket, int32_t* counts, double* w,
                           int32_t* status, void* stream);
 
+/* Shrinkage intensity of every date's window towards mean(diag S) I (Ledoit-Wolf 2004:
+ * kind 0; OAS, Chen et al. 2010: kind 1) from the band Gram of pq_lr_band_gram (band, ldo,
+ * r0, nrows, W as there).  Date b's window is the panel rows rows[b][0 .. tlen[b]) (strictly
+ * increasing, not necessarily consecutive; entries past tlen[b] are never read); with
+ * K = Xc Xc' (centred != 0: the window minus its own column means, formed from the band's
+ * row sums) or X X' (centred == 0), T = tlen[b] and n the number of assets,
+ *   stats[b] = { a = tr K, f = sum_st K_st^2, g = sum_t K_tt^2, delta },
+ *   delta_LW  = clip((g - f/T) / (f - a^2/n), 0, 1), 0 where the denominator is <= 0,
+ *   delta_OAS = min(1, (f + a^2) / ((T+1) (f - a^2/n))), 1 where it is <= 0
+ * (sklearn's ledoit_wolf_shrinkage(X) and oas(X)[1]); Sigma* = (1 - delta) S + delta
+ * mean(diag S) I with mean(diag S) = a / (n (T - 1)).  One workgroup per date, two passes
+ * over the T (T+1) / 2 band entries of the half window, no floating-point atomics: the same
+ * input gives the same bits.  1 <= tmax <= 1024.  The row table is checked on the device
+ * (1 <= tlen <= tmax, rows inside [r0, r0 + nrows) and increasing, span <= W): a date that
+ * fails reads nothing from the band, its stats are NaN and the call returns an error after
+ * the kernel.  The call synchronises the stream (it reads that flag back); calls on
+ * different streams must not overlap.                                                     */
+int pq_shrink_stats_band(const double* band, int64_t ldo, int32_t r0, int32_t nrows, int32_t W,
+                         const int32_t* rows, int64_t ld_rows, const int32_t* tlen, int32_t tmax,
+                         int32_t batch, int32_t n, int32_t centred, int32_t kind, double* stats,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

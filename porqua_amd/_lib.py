@@ -226,6 +226,8 @@ _EXPORTS = {
                           c_dp, c_int64, c_dp, c_int32, c_int64, c_dp], c_int32),
     "pq_percentile_batched": ([c_dp, c_int64, c_int32, c_int32, ctypes.c_double, c_int32, c_dp, c_dp, c_dp,
                                c_dp, c_dp, c_dp, c_dp, c_dp, c_dp], c_int32),
+    "pq_shrink_stats_band": ([c_dp, c_int64, c_int32, c_int32, c_int32, c_dp, c_int64, c_dp, c_int32, c_int32,
+                              c_int32, c_int32, c_int32, c_dp, c_dp], c_int32),
 }
 
 _lib = None

@@ -9,7 +9,9 @@
 DataFrame out) and computes the two-pass np.cov / DataFrame.cov() result with K1
 (window mean + FP64-MFMA SYRK; windows with NaN: pandas' pairwise-complete covariance from
 four masked MFMA Grams), the PD check with K2's Cholesky info and the repair with
-``helper_functions.nearestPD``.  ``estimate_batch`` is the batched backtest entry: all
+``helper_functions.nearestPD``.  Beyond the reference's methods, 'ledoit_wolf' and 'oas' shrink
+towards mean(diag S) I with a data-driven intensity per window (engine.shrinkage_intensity:
+three sums over the window's T x T Gram).  ``estimate_batch`` is the batched backtest entry: all
 rebalance dates of a device-resident panel at once, results left on the device.
 """
 from __future__ import annotations
@@ -39,10 +41,19 @@ def _shrink_lambda(lam):
     return float(lam)
 
 
+# data-driven shrinkage towards mean(diag S) I: Sigma* = (1 - delta) S + delta mean(diag S) I
+SHRINKAGE_METHODS = ("ledoit_wolf", "oas")
+
+
 class Covariance:
+    """``shrinkage_``: the intensity delta of the last ``estimate`` with a SHRINKAGE_METHODS
+    method (float); ``shrinkage_batch_``: the (B,) device tensor of the last batched estimate
+    with one, None after any other method."""
 
     def __init__(self, spec: CovarianceSpecification = None, *args, **kwargs):
         self.spec = CovarianceSpecification(*args, **kwargs) if spec is None else spec
+        self.shrinkage_ = None
+        self.shrinkage_batch_ = None
 
     def set_ctrl(self, *args, **kwargs) -> None:
         self.spec = CovarianceSpecification(*args, **kwargs)
@@ -55,6 +66,8 @@ class Covariance:
             covmat = cov_duv(X)
         elif method == "linear_shrinkage":
             covmat = cov_linear_shrinkage(X, self.spec.get("lambda_covmat_regularization"))
+        elif method in SHRINKAGE_METHODS:
+            covmat, self.shrinkage_ = _cov_shrunk(X, method)
         else:
             raise NotImplementedError("This method is not implemented yet")
         if self.spec.get("check_positive_definite") and not isPD(covmat):
@@ -85,12 +98,15 @@ class Covariance:
         S): S is None and dg = diag(Xc'Xc) per date carries what the shrinkage term needs."""
         import torch
         method = self.spec["method"]
+        self.shrinkage_batch_ = None
         if method == "duv":
             return None, None, None, None
-        if method not in ("pearson", "linear_shrinkage"):
+        if method not in ("pearson", "linear_shrinkage") + SHRINKAGE_METHODS:
             raise NotImplementedError("This method is not implemented yet")
         B, n = int(rows.shape[0]), panel.n
         if panel.has_nan:
+            if method in SHRINKAGE_METHODS:   # complete windows only: the serial loop reports it
+                return None, None, None, None
             return self._estimate_batch_pairwise(panel, rows, tlen, out, method)
         S = dg = None
         if not materialise and groups is not None and groups.ok:
@@ -115,6 +131,14 @@ class Covariance:
                     pdiag = lam * torch.diagonal(S, dim1=1, dim2=2)[:, :n].mean(dim=1)
                 else:   # mean(diag S) = mean(diag Xc'Xc) / (T - 1)
                     pdiag = lam * dg[:, :n].mean(dim=1) / (tlen.to(torch.float64) - 1.0)
+        elif method in SHRINKAGE_METHODS:
+            from . import engine
+            delta, _ = engine.shrinkage_intensity(panel, rows, tlen, kind=method)
+            self.shrinkage_batch_ = delta
+            if S is not None:
+                pdiag = delta * torch.diagonal(S, dim1=1, dim2=2)[:, :n].mean(dim=1)
+            else:
+                pdiag = delta * dg[:, :n].mean(dim=1) / (tlen.to(torch.float64) - 1.0)
         return S, pdiag, mu, dg
 
 
@@ -181,3 +205,32 @@ def cov_linear_shrinkage(X, lambda_covmat_regularization=None):
         vals = vals + lam * np.mean(np.diag(vals)) * np.eye(d)
         S = pd.DataFrame(vals, index=S.index, columns=S.columns) if isinstance(S, pd.DataFrame) else vals
     return S
+
+
+def _cov_shrunk(X, method):
+    """(Sigma*, delta) of one complete window: the sample covariance (K1) shrunk towards
+    mean(diag S) I by the intensity of engine.shrinkage_intensity."""
+    from . import engine
+    Xv = np.ascontiguousarray(X.to_numpy() if hasattr(X, "to_numpy") else X, dtype=np.float64)
+    if np.isnan(Xv).any():
+        raise ValueError(f"{method} shrinkage needs complete windows")
+    T, n = Xv.shape
+    pan = engine.Panel(Xv)
+    rows, tlen = pan.rows_to_device(np.arange(T, dtype=np.int32)[None], np.array([T], dtype=np.int32))
+    S = pan.cov(rows, tlen, mode=0)[0, :n, :n].cpu().numpy()
+    delta = float(engine.shrinkage_intensity(pan, rows, tlen, kind=method)[0][0].item())
+    S = (1.0 - delta) * S + delta * np.mean(np.diag(S)) * np.eye(n)
+    if isinstance(X, pd.DataFrame):
+        S = pd.DataFrame(S, index=X.columns, columns=X.columns)
+    return S, delta
+
+
+def cov_ledoit_wolf(X):
+    """Ledoit-Wolf (2004) shrinkage of the sample covariance towards mean(diag S) I with the
+    intensity of sklearn's ledoit_wolf_shrinkage (applied to the ddof = 1 covariance)."""
+    return _cov_shrunk(X, "ledoit_wolf")[0]
+
+
+def cov_oas(X):
+    """Oracle approximating shrinkage (Chen et al. 2010), sklearn's oas intensity."""
+    return _cov_shrunk(X, "oas")[0]

@@ -584,6 +584,16 @@ def _retry_set(ws: "Workspace", settings: Settings):
     return bad.contiguous(), m, settings.to_c(eps_abs=settings.eps_retry, eps_rel=settings.eps_retry)
 
 
+def _window_span(rows, tlen):
+    """(r0, nrows, W) of a device row table: the panel rows the windows touch and the widest
+    window span (one host read)."""
+    t = tlen.to(torch.int64)
+    first = rows[:, 0].to(torch.int64)
+    last = rows.gather(1, (t - 1).clamp(min=0)[:, None]).flatten().to(torch.int64)
+    v = torch.stack([first.min(), last.max(), (last - first + 1).max()]).cpu().tolist()
+    return int(v[0]), int(v[1] - v[0] + 1), int(v[2])
+
+
 class LowRank:
     """Device description of P_eff = p_scale w_scale Xc'Xc + p_diag I through the date
     windows (pq_lowrank): nothing n x n is formed.  ``mu`` None = uncentred Gram
@@ -603,11 +613,7 @@ class LowRank:
     def span(self):
         """(r0, nrows, W): the panel rows the windows touch and the widest window span."""
         if self._span is None:
-            t = self.tlen.to(torch.int64)
-            first = self.rows[:, 0].to(torch.int64)
-            last = self.rows.gather(1, (t - 1).clamp(min=0)[:, None]).flatten().to(torch.int64)
-            v = torch.stack([first.min(), last.max(), (last - first + 1).max()]).cpu().tolist()
-            self._span = (int(v[0]), int(v[1] - v[0] + 1), int(v[2]))
+            self._span = _window_span(self.rows, self.tlen)
         return self._span
 
     def c_struct(self) -> _lib.PQLowRank:
@@ -804,6 +810,43 @@ def _band_setup(qb: QPBatch, lr: LowRank, strm, w_min: int = 0):
     return {"band": band, "ldo": ldo, "r0": r0, "pc": pc, "cc": cc, "W": W, "nrows": nrows,
             "cap": (band.data_ptr(), ldo, r0, pc.data_ptr(), pc.stride(0)),
             "admm": (pc.data_ptr(), pc.stride(0), r0, cc.data_ptr())}
+
+
+SHRINKAGE_KINDS = {"ledoit_wolf": 0, "oas": 1}
+
+
+def shrinkage_intensity(panel: "Panel", rows, tlen, kind: str = "ledoit_wolf", centred: bool = True):
+    """Data-driven shrinkage intensity of every window towards mean(diag S) I (Ledoit-Wolf
+    2004 or OAS, Chen et al. 2010: sklearn's ledoit_wolf_shrinkage / oas) -> (delta (B,),
+    stats (B, 4) = a, f, g, delta), device tensors.  ``rows`` / ``tlen``: the device row table
+    (Panel.rows_to_device), complete windows.  The band Gram of the rows the windows touch
+    (pq_lr_band_gram, W = the widest span) is rebuilt on every call -- the panel may have
+    changed -- into a buffer kept with the panel; pq_shrink_stats_band then reads each date's
+    T x T window Gram from it.  Synchronises (the kernel's row-table check is read back)."""
+    if kind not in SHRINKAGE_KINDS:
+        raise ValueError(f"shrinkage_intensity: unknown kind {kind!r} (expected one of {sorted(SHRINKAGE_KINDS)})")
+    lib = _lib.load()
+    B, tmax = int(rows.shape[0]), int(rows.shape[1])
+    dev = panel.device
+    stats = torch.empty((B, 4), dtype=F64, device=dev)
+    if B == 0:
+        return stats[:, 3].contiguous(), stats
+    r0, nrows, W = _cached(panel, "_c_shrink_span", _tkey(rows, tlen), lambda: _window_span(rows, tlen),
+                           keep=(rows, tlen))
+    if r0 < 0 or r0 + nrows > panel.D or W < 1:
+        raise ValueError("shrinkage_intensity: the row table points outside the panel")
+    ldo = round_up(W, 2)
+    band = _cached(panel, "_c_shrink_band", (nrows, ldo),
+                   lambda: torch.empty((nrows, ldo), dtype=F64, device=dev))
+    R = panel.R
+    strm = _stream()
+    _lib.check(lib.pq_lr_band_gram(R.data_ptr(), R.stride(0), panel.n, r0, nrows, W, band.data_ptr(), ldo,
+                                   None, 0, 0, None, 0, strm), "pq_lr_band_gram")
+    rows = rows.contiguous()   # row pitch tmax, as every window entry point reads the table
+    _lib.check(lib.pq_shrink_stats_band(band.data_ptr(), ldo, r0, nrows, W, rows.data_ptr(), tmax,
+                                        tlen.data_ptr(), tmax, B, panel.n, int(bool(centred)),
+                                        SHRINKAGE_KINDS[kind], stats.data_ptr(), strm), "pq_shrink_stats_band")
+    return stats[:, 3].contiguous(), stats
 
 
 def _group_uniform(qb: QPBatch, lr: "LowRank", groups: "GroupPlan") -> bool:

@@ -166,12 +166,16 @@ class MeanVariance(Optimization):
         dev = stage.device
         if nan and S is None:
             return None
+        # 'ledoit_wolf' / 'oas': Sigma* = (1 - delta) S + pdiag I with a per-date delta; the
+        # factor (1 - delta) goes into w_scale (window form) or the returned scale (dense)
+        delta = getattr(self.covariance, "shrinkage_batch_", None)
         if mu_c is None and not nan:  # duv: identity covariance
             S = stage.identity_P()
             pdiag = torch.zeros(B, dtype=torch.float64, device=dev)
         elif lowrank:   # factored form S = Xc'Xc / (T - 1) for the Woodbury solver (no n x n S)
             stage.lowrank = engine.LowRank(stage.panel, stage.rows, stage.tlen, mu=mu_c,
-                                           w_scale=1.0 / (stage.tlen.to(torch.float64) - 1.0), dg=dg)
+                                           w_scale=(1.0 if delta is None else 1.0 - delta)
+                                           / (stage.tlen.to(torch.float64) - 1.0), dg=dg)
         me = self.mean_estimator
         if me.spec.get("method") != "geometric":
             return None
@@ -192,7 +196,7 @@ class MeanVariance(Optimization):
         if sf not in (None, 1):
             mu = torch.expm1(torch.log1p(mu) * sf)
         scale = torch.full((B,), 2.0 * ra, dtype=torch.float64, device=dev)
-        return S, scale, scale * pdiag, -mu, None
+        return S, scale if delta is None or lowrank else scale * (1.0 - delta), scale * pdiag, -mu, None
 
 
 class QEQW(Optimization):

@@ -29,12 +29,20 @@ F64 = torch.float64
 class MinVarianceBacktest:
     """Config 3 on one device: dates ``[rank * D, (rank + 1) * D)`` of a panel of
     ``T - 1 + D * world`` rows (weak scaling) or, with ``strong=True``, the rank's share of
-    ``D`` dates in total (strong scaling, contiguous blocks)."""
+    ``D`` dates in total (strong scaling, contiguous blocks).  ``shrinkage`` ('ledoit_wolf' or
+    'oas', default None = the benchmark's problem): P = 2 Sigma* with the per-date shrinkage
+    intensity recomputed every step."""
 
     def __init__(self, n: int = 1000, T: int = 252, D: int = 4749, rank: int = 0, world: int = 1,
                  device=None, settings: engine.Settings | None = None, path: str = "auto",
                  group: bool = True, slide: bool = True, with_cov: bool = False, strong: bool = False,
-                 seed: int | None = None, graph: bool = False):
+                 seed: int | None = None, graph: bool = False, shrinkage: str | None = None):
+        if shrinkage is not None and shrinkage not in engine.SHRINKAGE_KINDS:
+            raise ValueError(f"shrinkage must be None or one of {sorted(engine.SHRINKAGE_KINDS)}")
+        # 'ledoit_wolf' / 'oas': P = 2 ((1 - delta) S + delta mean(diag S) I) with the per-date
+        # intensity recomputed every step (engine.shrinkage_intensity); such steps run eagerly
+        self.shrinkage = shrinkage
+        self.delta = None   # the last step's intensities, (D,) on the device
         self.n, self.T = n, T
         # graph mode: the step's stages are sync-free and captured as HIP graphs after a first
         # eager step (engine.StageGraphs), on a stream of its own
@@ -78,6 +86,8 @@ class MinVarianceBacktest:
         self.mu = self.pan.window_means(self.rows_d, self.tlen_d)
         self.w_scale = 1.0 / (self.tlen_d.to(F64) - 1.0)
         self.lr = engine.LowRank(self.pan, self.rows_d, self.tlen_d, mu=self.mu, w_scale=self.w_scale)
+        if shrinkage is not None:
+            qb.p_diag = torch.zeros((D,), dtype=F64, device=dev)
         self.use_lr = path == "lowrank" or (path == "auto" and engine.lowrank_applicable(qb, self.lr))
         self.with_cov = (not self.use_lr) or with_cov
         if self.with_cov:   # K1 writes Sigma every step (dense path: P = 2 Sigma is what K2 factors)
@@ -98,7 +108,7 @@ class MinVarianceBacktest:
         host-driven repairs only when something is left), every stage after the first step a
         replayed HIP graph on the workload's own stream (joined to the caller's stream on
         both sides, no host sync)."""
-        if not (self.graph and self.use_lr and self.grouped):
+        if not (self.graph and self.use_lr and self.grouped) or self.shrinkage is not None:
             return self._step(events)
         if self.graphs is None:
             self.graphs = engine.StageGraphs()
@@ -141,18 +151,34 @@ class MinVarianceBacktest:
                 self.pan.cov(self.rows_d, self.tlen_d, mode=0, out=self.qb.P, mu=mu, plan=self.plan,
                              lower_only=self.use_lr)
         tl("moments+cov" if self.with_cov else "moments", moments)
+        if self.shrinkage is not None:
+            tl("shrinkage", self._shrink)
         if self.use_lr:
             return engine.solve_lowrank(self.qb, self.lr, self.settings, self.ws, events=events,
                                         groups=self.gplan, sync_free=self.graphs is not None,
                                         graphs=self.graphs, sf_rounds=self.sf_rounds)
         return engine.solve(self.qb, self.settings, self.ws, events=events)
 
+    def _shrink(self):
+        """The step's shrinkage stage: delta of every window, then P = 2 (1 - delta) S +
+        2 delta mean(diag S) I written in place -- (1 - delta) into w_scale (window path) or
+        p_scale (dense path), the ridge into qb.p_diag -- so the solve sees per-date values."""
+        delta, stats = engine.shrinkage_intensity(self.pan, self.rows_d, self.tlen_d, kind=self.shrinkage)
+        tm1 = self.tlen_d.to(F64) - 1.0
+        if self.use_lr:
+            torch.div(1.0 - delta, tm1, out=self.w_scale)
+        else:
+            torch.mul(1.0 - delta, 2.0, out=self.qb.p_scale)
+        # mean(diag S) = tr(Xc Xc') / (n (T - 1)): the kernel's a
+        torch.mul(delta, 2.0 * stats[:, 0] / (self.n * tm1), out=self.qb.p_diag)
+        self.delta = delta
+
     def certificate(self, res: engine.BatchResult, chunk: int = 256) -> dict:
         lb = torch.zeros(self.n, dtype=F64, device=self.device)
         ub = torch.ones(self.n, dtype=F64, device=self.device)
         return window_certificate(self.pan.R, self.rows_d, self.tlen_d, self.mu, self.qb.p_scale * self.w_scale,
                                   self.qb.q[:, :self.n], res, A_row=torch.ones(self.n, dtype=F64, device=self.device),
-                                  b=1.0, lb=lb, ub=ub, chunk=chunk)
+                                  b=1.0, lb=lb, ub=ub, chunk=chunk, p_diag=self.qb.p_diag)
 
 
 class _LSTrackingBatch:
