@@ -231,8 +231,10 @@ int pq_init_state_lr(const pq_lowrank* lr, const pq_problem* pb, pq_state* st, c
                      int32_t nidx, const pq_settings* s, void* stream);
 
 /* K2: form K = P_eff + sigma I + Cg' R Cg + R_box for the current rho, factor it with a
- * batched blocked Cholesky on FP64 MFMA (info[] = first failing column + 1, the isPD test
- * of src/helper_functions.py:61-67), and if `invert` overwrite K with K^-1 (trtri+lauum):
+ * batched blocked Cholesky on FP64 MFMA (info[] is nonzero iff K is not positive definite,
+ * the isPD test of src/helper_functions.py:61-67; it names the 16-column block of the first
+ * failing pivot c: info = 1 + 16 * (c / 16), with status PQ_NON_CONVEX -- every route, and
+ * pq_factor_large), and if `invert` overwrite K with K^-1 (trtri+lauum):
  * invert = 1 writes the lower triangle only (what pq_admm_batched reads), invert = 2 the
  * full symmetric matrix.  With mg = 0, lb = ub = NULL and sigma = 0 this is a plain
  * batched potrf of P_eff.                                                              */

@@ -268,8 +268,10 @@ constexpr int CHOL_LDS = 4 * STAGE + TB * LDW;
 
 // Factor the nb*64 x nb*64 matrix whose lower-triangle elements are produced by
 // `form(gi, gj)` (read exactly once each) into L stored in K (ld), with the transposed
-// inverses of the diagonal blocks in Dt.  Returns info (0 = success, else first failing
-// column + 1).  All threads of the (256-thread) workgroup must call it.
+// inverses of the diagonal blocks in Dt.  Returns info: 0 = success, nonzero iff the matrix
+// is not positive definite, and then 1 + the first column of the 16-column block that holds
+// the first failing pivot (tile_chol_inv64).  All threads of the (256-thread) workgroup must
+// call it.
 // kStoreDiag = false leaves K's diagonal 64x64 blocks untouched (nothing downstream of the
 // polish reads them: the solves use Dt), so they can keep the matrix being factored.
 template <bool kStoreDiag = true, typename Form>

@@ -20,7 +20,8 @@
 // n = 2048) -- the parallelism a single large problem needs.  Total FP64 work n^3/3 (potrf)
 // + n^3/3 (trtri) + n^3/3 (lauum) on v_mfma_f64_16x16x4, tiles staged through LDS by the
 // shared gemm_stream machinery (common.h).  A problem whose diagonal block fails (not PD)
-// records info = first failing column + 1 and status PQ_NON_CONVEX; its later launches
+// records a nonzero info (1 + the first column of the 16-column block that holds the first
+// failing pivot, pq_factor_batched's contract) and status PQ_NON_CONVEX; its later launches
 // return at once.
 #include "chol_dev.h"
 #include "capi_util.h"

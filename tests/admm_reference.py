@@ -27,7 +27,11 @@ every solve takes three steps of iterative refinement on longdouble residuals.
 ``admm_woodbury_f64`` is the same iteration in float64 through the kernels' own algebra,
 K^-1 = (I - V' M^-1 V / d) / d with an explicit inverse of the capacitance M = I + V V' / d.
 Its distance from the dense model measures the rounding that algebra amplifies: it is the
-yardstick of tests/test_admm_iterates_gpu.py and nothing else.
+yardstick of tests/test_admm_iterates_gpu.py and nothing else.  ``admm_explicit_inverse_f64``
+plays the same role for the dense kernels (pq_factor_batched + pq_admm_batched,
+tests/test_dense_admm_iterates_gpu.py): float64 with an explicit K^-1 = L^-T L^-1.
+``kkt_matrix`` is the one place K is formed (also the reference of
+tests/test_kkt_factor_gpu.py).
 """
 from __future__ import annotations
 
@@ -61,7 +65,8 @@ def _amax(*vs):
 
 
 def _iterate(q, Cg, lg, ug, lb, ub, rho, st, iters, dt, make_solver):
-    """The iteration itself; make_solver(rg, rb) -> (rhs -> K^-1 rhs) for the current rho."""
+    """The iteration itself; make_solver(rg, rb, rho) -> (rhs -> K^-1 rhs) for the current rho
+    (rg, rb: its per-row values)."""
     n = q.shape[0]
     Cg = np.asarray(Cg, dtype=dt).reshape(-1, n)
     mg = Cg.shape[0]
@@ -74,13 +79,13 @@ def _iterate(q, Cg, lg, ug, lb, ub, rho, st, iters, dt, make_solver):
 
     def rows(rho):
         rg, rb = row_rho(lg, ug, rho, st).astype(dt), row_rho(lb, ub, rho, st).astype(dt)
-        return rg, rb, make_solver(rg, rb)
+        return rg, rb, make_solver(rg, rb, rho)
 
     rg, rb, solve = rows(rho)
     x, Px, zb, yb = (np.zeros(n, dt) for _ in range(4))
     zg, yg = np.zeros(mg, dt), np.zeros(mg, dt)
     qmax = _amax(q)
-    hist, rhos, it, status = [], [], 0, "unsolved"
+    hist, rhos, cands, it, status = [], [], [], 0, "unsolved"
     end = min(int(iters), int(st.max_iter))
     while it < end:
         it += 1
@@ -112,6 +117,7 @@ def _iterate(q, Cg, lg, ug, lb, ub, rho, st, iters, dt, make_solver):
         if st.adapt_interval > 0 and it % st.adapt_interval == 0 and it < st.max_iter:
             rn = rho * np.sqrt((rp / (sp + 1e-30)) / (rd / (sd + 1e-30) + 1e-30))
             rn = min(max(float(rn), st.rho_min), st.rho_max)
+            cands.append((it, rn, rho))
             if rn > rho * st.adapt_tol or rn < rho / st.adapt_tol:
                 rho = rn
                 rg, rb, solve = rows(rho)
@@ -119,15 +125,34 @@ def _iterate(q, Cg, lg, ug, lb, ub, rho, st, iters, dt, make_solver):
         if it >= st.max_iter:
             status = "max_iter"
     return SimpleNamespace(x=x, z=np.concatenate([zg, zb]), y=np.concatenate([yg, yb]), Px=Px, iters=it,
-                           status=status, rho=rho, hist=hist, rhos=rhos)
+                           status=status, rho=rho, hist=hist, rhos=rhos, cands=cands)
+
+
+def kkt_matrix(P, Cg, lg, ug, lb, ub, rho, settings, dtype=LD):
+    """K = P + sigma I + Cg' diag(rg) Cg + diag(rb) in ``dtype`` for an effective P (the one
+    place the test side forms it): rg / rb = row_rho of the general / box rows.  ``lb`` None:
+    no box rows."""
+    dt = np.dtype(dtype).type
+    P = np.asarray(P, dtype=dt)
+    n = P.shape[0]
+    Cgd = np.asarray(Cg, dtype=dt).reshape(-1, n)
+    mg = Cgd.shape[0]
+    rg = row_rho(np.reshape(lg, mg), np.reshape(ug, mg), rho, settings).astype(dt)
+    K = P + Cgd.T @ (rg[:, None] * Cgd)
+    d = dt(settings.sigma)
+    if lb is not None:
+        d = d + row_rho(np.reshape(lb, n), np.reshape(ub, n), rho, settings).astype(dt)
+    K[np.diag_indices(n)] += d
+    return K
 
 
 def admm_dense_ref(P, q, Cg, lg, ug, lb, ub, rho, settings=None, iters=None, dtype=LD):
     """``iters`` iterations (default: until the stop or max_iter) of the ADMM above for one
     problem, K solved densely in ``dtype`` (np.longdouble or np.float64).  Returns x, z and y
     (rows [general; box]), Px, iters, status ('solved', 'max_iter', 'unsolved': the budget
-    ran out), the final rho, ``hist``: (rp, eps_p, rd, eps_d) of every iteration, and ``rhos``: the
-    rho after every iteration that did not stop.
+    ran out), the final rho, ``hist``: (rp, eps_p, rd, eps_d) of every iteration, ``rhos``: the
+    rho after every iteration that did not stop, and ``cands``: (iteration, candidate rho, rho
+    before) of every adaptive-rho decision.
 
     P may be given in ``dtype`` already (form it once per date and scale it per problem: an
     extended-precision n^3 product per problem is slow)."""
@@ -137,9 +162,8 @@ def admm_dense_ref(P, q, Cg, lg, ug, lb, ub, rho, settings=None, iters=None, dty
     n = P.shape[0]
     Cgd = np.asarray(Cg, dtype=dt).reshape(-1, n)
 
-    def make_solver(rg, rb):
-        K = P + Cgd.T @ (rg[:, None] * Cgd)
-        K[np.diag_indices(n)] += dt(st.sigma) + rb
+    def make_solver(rg, rb, rho):
+        K = kkt_matrix(P, Cgd, lg, ug, lb, ub, rho, st, dt)
         lu = sla.lu_factor(np.asarray(K, dtype=np.float64))
         if dt is np.float64:
             return lambda rhs: sla.lu_solve(lu, rhs)
@@ -166,13 +190,29 @@ def admm_woodbury_f64(Xc, ps, q, Cg, lg, ug, lb, ub, rho, settings=None, iters=N
     n = Xc.shape[1]
     Cgd = np.asarray(Cg, dtype=np.float64).reshape(-1, n)
 
-    def make_solver(rg, rb):
+    def make_solver(rg, rb, rho):
         if not np.all(rb == rb[0]):
             raise ValueError("admm_woodbury_f64: the box rows must share one rho")
         dinv = 1.0 / (st.sigma + p_diag + rb[0])
         V = np.vstack([np.sqrt(ps) * Xc, np.sqrt(rg)[:, None] * Cgd])
         Minv = np.linalg.inv(np.eye(V.shape[0]) + (V @ V.T) * dinv)
         return lambda rhs: (rhs - V.T @ (Minv @ (V @ (rhs * dinv)))) * dinv
+
+    return _iterate(np.asarray(q), Cg, lg, ug, lb, ub, rho, st, st.max_iter if iters is None else iters,
+                    np.float64, make_solver)
+
+
+def admm_explicit_inverse_f64(P, q, Cg, lg, ug, lb, ub, rho, settings=None, iters=None):
+    """The same iteration in float64 through the dense kernels' algebra (pq_factor_batched with
+    an inverse, then k_admm's symmetric mat-vec): K = L L' by numpy.linalg.cholesky,
+    K^-1 = L^-T L^-1 formed explicitly from inv(L), x~ = K^-1 rhs."""
+    st = settings or ref_settings()
+    P = np.asarray(P, dtype=np.float64)
+
+    def make_solver(rg, rb, rho):
+        Li = np.linalg.inv(np.linalg.cholesky(kkt_matrix(P, Cg, lg, ug, lb, ub, rho, st, np.float64)))
+        Kinv = Li.T @ Li
+        return lambda rhs: Kinv @ rhs
 
     return _iterate(np.asarray(q), Cg, lg, ug, lb, ub, rho, st, st.max_iter if iters is None else iters,
                     np.float64, make_solver)

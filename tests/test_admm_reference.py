@@ -1,12 +1,18 @@
 """tests/admm_reference.py (the dense extended-precision model the ADMM kernels' iterates are
 compared with, tests/test_admm_iterates_gpu.py) is itself checked here, without a GPU: run
 to convergence it reaches the oracle's optimum, its float64 and longdouble forms agree, and
-the Woodbury float64 yardstick is the same iteration."""
+the Woodbury float64 yardstick is the same iteration.  kkt_matrix (the one place the test
+side forms K) against a hand-built case, and the dense kernels' float64 yardstick
+(admm_explicit_inverse_f64) with the conditions tests/test_dense_admm_iterates_gpu.py rests on."""
 import numpy as np
+import pytest
+import scipy.linalg as sla
 
 from oracle.qp_ipm import solve_qp
 from porqua_amd.synthetic import factor_panel
-from tests.admm_reference import LD, admm_dense_ref, admm_woodbury_f64, ref_settings, rel_dist
+from tests import dense_cases
+from tests.admm_reference import (LD, _iterate, admm_dense_ref, admm_explicit_inverse_f64, admm_woodbury_f64,
+                                  kkt_matrix, ref_settings, rel_dist)
 
 
 def _mean_variance(n, T, lam):
@@ -78,3 +84,92 @@ def test_reference_adaptive_rho_and_budget():
     assert a.rho != rho and st.rho_min <= a.rho <= st.rho_max
     b = admm_dense_ref(P, q, Cg, lg, ug, lb, ub, rho, st, iters=5)
     assert b.iters == 5 and b.status == "unsolved" and b.hist == a.hist[:5]
+
+
+def test_kkt_matrix_hand_built_rows_of_every_kind():
+    """3 x 3, general rows: equality, one-sided, two-sided, unbounded; box: two-sided, fixed, free."""
+    inf = np.inf
+    P = np.array([[2.0, 0.5, 0.0], [0.5, 3.0, 0.25], [0.0, 0.25, 4.0]])
+    Cg = np.array([[1.0, 1.0, 1.0], [1.0, 0.0, 2.0], [0.0, 1.0, -1.0], [3.0, 0.0, 1.0]])
+    lg, ug = [1.0, -inf, -0.2, -inf], [1.0, 0.5, 0.3, inf]
+    lb, ub = [0.0, 0.1, -inf], [1.0, 0.1, inf]
+    st = ref_settings(sigma=1e-3, eq_scale=1e3, rho_min=1e-2)
+    rho, eq, mn, sg = 0.5, 0.5 * 1e3, 1e-2, 1e-3
+    # P + eq c0 c0' + rho c1 c1' + rho c2 c2' + rho_min c3 c3' (+ sigma + box rho on the diagonal)
+    K = np.array([[2.0 + eq + rho * 1.0 + 0.0 + mn * 9.0, 0.5 + eq, 0.0 + eq + rho * 2.0 + mn * 3.0],
+                  [0.0, 3.0 + eq + 0.0 + rho * 1.0, 0.25 + eq - rho * 1.0],
+                  [0.0, 0.0, 4.0 + eq + rho * 4.0 + rho * 1.0 + mn * 1.0]])
+    K = K + np.triu(K, 1).T
+    box = np.diag([sg + rho, sg + eq, sg + mn])
+    tol = 1e-12   # the expected values are float64 sums of magnitude 1e3; the smallest weight is 1e-2
+    for dt in (LD, np.float64):
+        got = kkt_matrix(P, Cg, lg, ug, lb, ub, rho, st, dt)
+        assert got.dtype == dt and np.abs(got - (K + box)).max() <= tol, np.abs(got - (K + box)).max()
+        nobox = kkt_matrix(P, Cg, lg, ug, None, None, rho, st, dt)
+        assert np.abs(nobox - (K + sg * np.eye(3))).max() <= tol
+        # no general rows: mg = 0
+        assert np.array_equal(kkt_matrix(P, np.zeros((0, 3)), [], [], None, None, rho, st, dt),
+                              P.astype(dt) + np.diag(np.full(3, dt(sg))))
+    # a wrong weight on any kind of row would show: the four kinds' weights all differ
+    assert len({eq, rho, mn}) == 3
+
+
+def test_dense_ref_unchanged_by_kkt_matrix():
+    """admm_dense_ref forms K through kkt_matrix: the iterates equal, bit for bit, those of the
+    formation it had inline (K = P + Cg' diag(rg) Cg, then sigma + rb on the diagonal)."""
+    n, T = 60, 20
+    st = ref_settings(eps_abs=1e-12, eps_rel=1e-12, adapt_interval=4, adapt_tol=1.5, max_iter=12)
+    Xc, ps, P, q, rho = _mean_variance(n, T, 1.0)
+    Cg, lg, ug = np.ones((1, n)), [1.0], [1.0]
+    lb, ub = np.zeros(n), np.ones(n)
+    ub[3], lb[5], ub[5] = np.inf, -np.inf, np.inf
+    Cgd = Cg.astype(LD)
+
+    def inline(rg, rb, rho):
+        K = P + Cgd.T @ (rg[:, None] * Cgd)
+        K[np.diag_indices(n)] += LD(st.sigma) + rb
+        lu = sla.lu_factor(np.asarray(K, dtype=np.float64))
+
+        def solve(rhs):
+            x = sla.lu_solve(lu, np.asarray(rhs, dtype=np.float64)).astype(LD)
+            for _ in range(3):
+                x = x + sla.lu_solve(lu, np.asarray(rhs - K @ x, dtype=np.float64)).astype(LD)
+            return x
+        return solve
+
+    a = admm_dense_ref(P, q, Cg, lg, ug, lb, ub, rho, st)
+    b = _iterate(q, Cg, lg, ug, lb, ub, rho, st, st.max_iter, LD, inline)
+    assert a.rho != rho and a.rhos == b.rhos and a.hist == b.hist
+    for k in ("x", "z", "y", "Px"):
+        assert np.array_equal(getattr(a, k), getattr(b, k)), k
+
+
+DENSE_CASES = [(n, c) for n in (24, 130, 300) for c in (True, False)]   # (the larger ones: on the GPU run)
+
+
+@pytest.mark.parametrize("n,centred", DENSE_CASES)
+def test_explicit_inverse_model_distance_and_edges(n, centred):
+    """The conditions the dense iterate test rests on, by the reference alone: after 7
+    iterations the float64 explicit-inverse model is within 1e-9 of the longdouble model for x,
+    z and y (so the 10 d_model bar is never looser than 1e-8; measured <= 4.7e-10 at n <= 130
+    and <= 1e-10 beyond) and within 1e-6 for Px (measured <= 2.9e-7); no stop decision of the
+    stop-rule run and no accept / reject decision of the adaptive-rho run is within 1e-3 of its
+    threshold (measured >= 9.8e-3 and >= 1e-1), and every problem adapts, at iteration 8."""
+    from porqua_amd import engine   # (Settings only: host-side defaults of rho0_rel, rho0_qrel)
+    case = dense_cases.portfolio_batch(n, 5, centred)
+    st = engine.Settings(eps_abs=1e-12, eps_rel=1e-12, adapt_interval=0, max_iter=7)
+    rho = dense_cases.initial_rho(case, st)
+    assert rho.max() / rho.min() > 1.1
+    ref, mod = dense_cases.references(case, st, rho)
+    d = {k: max(rel_dist(getattr(m, k), getattr(r, k)) for r, m in zip(ref, mod)) for k in ("x", "z", "y", "Px")}
+    print("d_model", n, centred, {k: "%.1e" % v for k, v in d.items()})
+    assert all(r.iters == 7 and r.status == "max_iter" for r in ref + mod)
+    assert max(d["x"], d["z"], d["y"]) <= 1e-9 and d["Px"] <= 1e-6, d
+    st = engine.Settings(eps_abs=1.6e-3, eps_rel=1.6e-3, adapt_interval=0, min_iter=3, max_iter=60)
+    ref, _ = dense_cases.references(case, st, rho, model=False)
+    assert dense_cases.stop_edge(ref) >= 1e-3 and all(3 <= r.iters < 60 and r.status == "solved" for r in ref)
+    st = engine.Settings(eps_abs=1e-12, eps_rel=1e-12, adapt_interval=4, adapt_tol=1.5, max_iter=12)
+    ref, mod = dense_cases.references(case, st, rho)
+    assert dense_cases.adapt_edge(ref, st) >= 1e-3
+    assert all(r.rho != r0 and [c[0] for c in r.cands] == [4, 8] for r, r0 in zip(ref, rho))
+    assert max(abs(m.rho / r.rho - 1.0) for r, m in zip(ref, mod)) <= 1e-8
