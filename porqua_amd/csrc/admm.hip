@@ -15,7 +15,7 @@
 //
 // Replaces qpsolvers.solve_problem(...) (src/qp_problems.py:211-214) for the dense QPs
 // PorQua builds in Optimization.model_qpsolvers (src/optimization.py:91-143).
-#include "common.h"
+#include "admm_dev.h"
 #include "capi_util.h"
 
 namespace pq {
@@ -51,12 +51,6 @@ struct PhaseClock {
   __device__ void flush(double*) {}
 #endif
 };
-
-__device__ __forceinline__ double rho_row(double l, double u, double rho, const pq_settings& s) {
-  if (l == u) return rho * s.eq_scale;
-  if (isinf(l) && isinf(u)) return s.rho_min;
-  return rho;
-}
 
 // multi-value workgroup max: v[0..NV) per thread -> out[0..NV) for every thread
 template <int NV>
@@ -211,7 +205,7 @@ __device__ void lr_apply(const pq_lowrank& lr, int b, const pq_problem& pb, cons
   // (1) v = D^-1 rhs
   for (int i = t; i < LDMAX; i += AT) {
     double d = 0.0;
-    if (i < n) d = rhs[i] / (s.sigma + pd + (has_box ? rho_row(lo[i], up[i], rho, s) : 0.0));
+    if (i < n) d = rhs[i] / (s.sigma + pd + (has_box ? row_rho(lo[i], up[i], rho, s) : 0.0));
     vv[i] = d;
   }
   __syncthreads();
@@ -335,7 +329,7 @@ __device__ void lr_apply(const pq_lowrank& lr, int b, const pq_problem& pb, cons
   for (int i = t; i < n; i += AT) {
     double corr = sps * (xt[i] - (mu ? su * mu[i] : 0.0));
     for (int r = 0; r < mg; ++r) corr = fma(sqrt(rg[r]) * ku[tmax + r], Cg[(int64_t)r * ld + i], corr);
-    const double D = s.sigma + pd + (has_box ? rho_row(lo[i], up[i], rho, s) : 0.0);
+    const double D = s.sigma + pd + (has_box ? row_rho(lo[i], up[i], rho, s) : 0.0);
     xt[i] = vv[i] - corr / D;
   }
   __syncthreads();
@@ -415,7 +409,7 @@ __global__ __launch_bounds__(AT) void k_admm(pq_problem pb, pq_state st, const i
       yg[t] = gyg[t];
       lgs[t] = lgv;
       ugs[t] = ugv;
-      rg[t] = rho_row(lgv, ugv, rho, s);
+      rg[t] = row_rho(lgv, ugv, rho, s);
     }
   }
   __syncthreads();
@@ -434,7 +428,7 @@ __global__ __launch_bounds__(AT) void k_admm(pq_problem pb, pq_state st, const i
     __syncthreads();
     for (int i = t; i < n; i += AT) {
       double r = sigma * x[i] - q[i];
-      if (has_box) r += rho_row(lo[i], up[i], rho, s) * zb[i] - yb[i];
+      if (has_box) r += row_rho(lo[i], up[i], rho, s) * zb[i] - yb[i];
       for (int k = 0; k < mg; ++k) r += Cg[(int64_t)k * ld + i] * wg[k];
       rhs[i] = r;
     }
@@ -458,7 +452,7 @@ __global__ __launch_bounds__(AT) void k_admm(pq_problem pb, pq_state st, const i
       double pxt = rhs[i] - sigma * xti;
       double rb = 0.0;
       if (has_box) {
-        rb = rho_row(lo[i], up[i], rho, s);
+        rb = row_rho(lo[i], up[i], rho, s);
         pxt -= rb * xti;
       }
       for (int k = 0; k < mg; ++k) pxt -= Cg[(int64_t)k * ld + i] * rg[k] * ztg[k];
@@ -468,9 +462,8 @@ __global__ __launch_bounds__(AT) void k_admm(pq_problem pb, pq_state st, const i
       Px[i] = pxn;
       double cty = 0.0;
       if (has_box) {
-        const double zh = alpha * xti + (1.0 - alpha) * zb[i];
-        const double zn = fmin(fmax(zh + yb[i] / rb, lo[i]), up[i]);
-        const double yn = yb[i] + rb * (zh - zn);
+        const RowStep rs = row_step(xti, zb[i], yb[i], rb, lo[i], up[i], alpha);
+        const double zn = rs.zn, yn = rs.yn;
         zb[i] = zn;
         yb[i] = yn;
         cty = yn;
@@ -486,10 +479,9 @@ __global__ __launch_bounds__(AT) void k_admm(pq_problem pb, pq_state st, const i
     }
     __syncthreads();
     if (t < mg) {
-      const double zh = alpha * ztg[t] + (1.0 - alpha) * zg[t];
-      const double zn = fmin(fmax(zh + yg[t] / rg[t], lgs[t]), ugs[t]);
-      yg[t] = yg[t] + rg[t] * (zh - zn);
-      zg[t] = zn;
+      const RowStep rs = row_step(ztg[t], zg[t], yg[t], rg[t], lgs[t], ugs[t], alpha);
+      yg[t] = rs.yn;
+      zg[t] = rs.zn;
       cgx[t] = alpha * ztg[t] + (1.0 - alpha) * cgx[t];
     }
     __syncthreads();
@@ -507,28 +499,15 @@ __global__ __launch_bounds__(AT) void k_admm(pq_problem pb, pq_state st, const i
     }
     block_maxv<8>(mv, red);
     pc.stamp(5);
-    const double eps_p = s.eps_abs + s.eps_rel * fmax(mv[1], mv[2]);
-    const double eps_d = s.eps_abs + s.eps_rel * fmax(mv[4], fmax(mv[5], mv[6]));
-    if (it >= s.min_iter && mv[0] <= eps_p && mv[3] <= eps_d) {
-      status = PQ_SOLVED;
+    const Verdict vd = verdict(mv, it, rho, s);
+    if (vd.status != PQ_UNSOLVED) {   // solved, a new rho to factor, or max_iter (= it_end)
+      status = vd.status;
+      rho = vd.rho;
       break;
-    }
-    // (not at max_iter itself: the run ends there, and a rho request would cost a
-    // refactorisation that no iteration uses)
-    if (s.adapt_interval > 0 && it % s.adapt_interval == 0 && it < s.max_iter) {
-      const double rp = mv[0] / (fmax(mv[1], mv[2]) + 1e-30);
-      const double rd = mv[3] / (fmax(mv[4], fmax(mv[5], mv[6])) + 1e-30);
-      double rn = rho * sqrt(rp / (rd + 1e-30));
-      rn = fmin(fmax(rn, s.rho_min), s.rho_max);
-      if (rn > rho * s.adapt_tol || rn < rho / s.adapt_tol) {
-        rho = rn;
-        status = PQ_NEED_REFACTOR;
-        break;
-      }
     }
     __syncthreads();
   }
-  if (status == PQ_UNSOLVED && it >= s.max_iter) status = PQ_MAX_ITER;
+  if (status == PQ_UNSOLVED && it >= s.max_iter) status = PQ_MAX_ITER;   // (no iteration ran)
   __syncthreads();
   pc.flush(st.work + (int64_t)b * st.work_stride + PQ_WORK_PROF(ld, st.mg_pad) + 16);
   // ---- save state --------------------------------------------------------------------

@@ -27,7 +27,8 @@
 //
 // Replaces qpsolvers.solve_problem (src/qp_problems.py:211-214) for the batched backtest,
 // like pq_admm_lr_grouped.
-#include "chol_dev.h"   // (common.h; tile_chol_inv64 for the H_b of m + 1 > 32)
+#include "admm_dev.h"
+#include "chol_dev.h"   // (tile_chol_inv64 for the H_b of m + 1 > 32)
 #include "capi_util.h"
 
 namespace pq {
@@ -60,22 +61,6 @@ constexpr int CH_MAX = 64;     // m + 1 = U - T + 1 <= 64
 #define CSTAMP(k) do { } while (0)
 #endif
 
-__device__ __forceinline__ double crho(double l, double u, double rho, const pq_settings& s) {
-  if (l == u) return rho * s.eq_scale;
-  if (isinf(l) && isinf(u)) return s.rho_min;
-  return rho;
-}
-__device__ __forceinline__ double csum32(double v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double cmax32(double v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // uniform ADMM diagonal d and the group constants of date b (rho = the group's)
 struct GConst {
   double c, sqc, d, rho;
@@ -86,7 +71,7 @@ __device__ __forceinline__ GConst gconst(const pq_lowrank& lr, const pq_problem&
   g.c = (pb.p_scale ? pb.p_scale[b] : 1.0) * (lr.w_scale ? lr.w_scale[b] : 1.0);
   g.sqc = sqrt(fmax(g.c, 0.0));
   const double pd = pb.p_diag ? pb.p_diag[b] : 0.0;
-  const double rb = pb.lb ? crho(pb.lb[(int64_t)b * pb.box_stride], pb.ub[(int64_t)b * pb.box_stride], rho, s) : 0.0;
+  const double rb = pb.lb ? row_rho(pb.lb[(int64_t)b * pb.box_stride], pb.ub[(int64_t)b * pb.box_stride], rho, s) : 0.0;
   g.d = s.sigma + pd + rb;
   g.rho = rho;
   return g;
@@ -110,7 +95,7 @@ __global__ __launch_bounds__(256) void k_gcap_assemble(pq_lowrank lr, pq_problem
   const int t = threadIdx.x, w = wave_id(), l = lane_id();
   for (int u = t; u < U; u += 256) s_w[u] = gc.urows[(int64_t)grp * gc.umax + u] - r0;
   const GConst g = gconst(lr, pb, s, d0, gc.grho[grp]);
-  if (t < mg) s_sr[t] = sqrt(crho(pb.lg[t], pb.ug[t], g.rho, s));
+  if (t < mg) s_sr[t] = sqrt(row_rho(pb.lg[t], pb.ug[t], g.rho, s));
   __syncthreads();
   const double a1 = g.c / g.d, a2 = g.sqc / g.d;
   double* M = gc.M + (int64_t)grp * gc.M_stride;
@@ -253,7 +238,7 @@ __global__ __launch_bounds__(PT_PREP, 2 / NB) void k_gcap_prep(pq_lowrank lr, pq
     s_T[t] = t < G ? lr.tlen[d0 + t] : 1;
   }
   const GConst g = gconst(lr, pb, s, d0, gc.grho[grp]);   // c, d, rho uniform in the group
-  if (t < mg) s_sr[t] = sqrt(crho(pb.lg[t], pb.ug[t], g.rho, s));
+  if (t < mg) s_sr[t] = sqrt(row_rho(pb.lg[t], pb.ug[t], g.rho, s));
   const int ktile = (kU + 15) >> 4;
   for (int e = t; e < (CK_MAX + 16) * CG; e += PT_PREP) s_a[e] = 0.0;
   __syncthreads();
@@ -561,7 +546,7 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
   __syncthreads();
   const double rho = s_rho;
   const GConst gk = gconst(lr, pb, s, d0, rho);
-  if (t < mg) s_sr[t] = sqrt(crho(pb.lg[t], pb.ug[t], rho, s));
+  if (t < mg) s_sr[t] = sqrt(row_rho(pb.lg[t], pb.ug[t], rho, s));
   if (t < CG) {
     const int g = t;
     int act = 0;
@@ -593,7 +578,7 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const bool ok = t < mg;
     g_lg[t] = ok ? pb.lg[t] : 0.0;
     g_ug[t] = ok ? pb.ug[t] : 0.0;
-    g_rg[t] = ok ? crho(pb.lg[t], pb.ug[t], rho, s) : 0.0;
+    g_rg[t] = ok ? row_rho(pb.lg[t], pb.ug[t], rho, s) : 0.0;
   }
   __syncthreads();
 
@@ -626,8 +611,8 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
         a = fma(Cg_h[(int64_t)r * ld + i], x_h[i], a);
         if (centred) am = fma(Cg_h[(int64_t)r * ld + i], mu_h[i], am);
       }
-      a = csum32(a);
-      am = csum32(am);
+      a = lanes_sum<32>(a);
+      am = lanes_sum<32>(am);
       if (hl == 0) {
         g_cgx[g * MGG + r] = a;
         g_cmu[g * MGG + r] = am;
@@ -638,7 +623,7 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
     double muv = 0.0, cvp[CMG] = {0.0, 0.0, 0.0, 0.0}, qmax = 0.0;
     for (int i = hl; i < n; i += 32) {
       qmax = fmax(qmax, fabs(q_h[i]));
-      const double rb = has_box ? crho(lo_h[i], up_h[i], rho, s) : 0.0;
+      const double rb = has_box ? row_rho(lo_h[i], up_h[i], rho, s) : 0.0;
       double rr = sigma * x_h[i] - q_h[i];
       if (has_box) rr += rb * zb_h[i] - yb_h[i];
       if constexpr (WIDE) {   // column-sparse rows (Cg V of the first iteration: pass 1)
@@ -660,10 +645,10 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
           if (r < mg) cvp[r] = fma(Cg_h[(int64_t)r * ld + i], v, cvp[r]);
       }
     }
-    muv = csum32(muv);
-    qmax = cmax32(qmax);
+    muv = lanes_sum<32>(muv);
+    qmax = lanes_max<32>(qmax);
 #pragma unroll
-    for (int r = 0; r < CMG; ++r) cvp[r] = csum32(cvp[r]);
+    for (int r = 0; r < CMG; ++r) cvp[r] = lanes_sum<32>(cvp[r]);
     if (hl == 0) {
       g_muv[g] = muv;
       g_qmax[g] = qmax;   // |q| (dual scale) is fixed over the iterations
@@ -871,7 +856,7 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
       const double* Hi = gc.hinv + (int64_t)b * gc.ldh * gc.ldh;
       double az = 0.0;
       for (int u = hl; u < kU; u += 32) az = fma(A[u], WU[u * CG + g], az);
-      az = csum32(az);
+      az = lanes_sum<32>(az);
       // s: lane j < m holds s_j = z'_{C_j}; lane m (or the last) holds s_mu
       double sj[2];
 #pragma unroll
@@ -1021,7 +1006,7 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
         for (int r = 0; r < mg; ++r) {
           double a = 0.0;
           for (int u = hl; u < U; u += 32) a = fma(pc[(int64_t)(s_urow[u] - r0) * ldpc + r], UT[u * CG + g], a);
-          a = csum32(a);
+          a = lanes_sum<32>(a);
           double cwv = 0.0;
           for (int r2 = 0; r2 < mg; ++r2) cwv = fma(cc[r * mg + r2], g_cw[g * MGG + r2], cwv);
           if (hl == 0) g_zt[g * MGG + r] = g_cgv[g * MGG + r] - dinv * (a - su * g_cmu[g * MGG + r] + cwv);
@@ -1031,9 +1016,8 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
         if (hl < mg) {
           const int e = g * MGG + hl;
           const double rg = g_rg[hl], zt = g_zt[e];
-          const double zh = alpha * zt + (1.0 - alpha) * g_zg[e];
-          const double zn = fmin(fmax(zh + g_yg[e] / rg, g_lg[hl]), g_ug[hl]);
-          const double yn = g_yg[e] + rg * (zh - zn);
+          const RowStep rs = row_step(zt, g_zg[e], g_yg[e], rg, g_lg[hl], g_ug[hl], alpha);
+          const double zn = rs.zn, yn = rs.yn;
           const double cx = alpha * zt + (1.0 - alpha) * g_cgx[e];
           gm[0] = fabs(cx - zn);
           gm[1] = fabs(cx);
@@ -1045,7 +1029,7 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
           g_wg[e] = rg * zn - yn;
         }
 #pragma unroll
-        for (int k = 0; k < 3; ++k) gm[k] = cmax32(gm[k]);
+        for (int k = 0; k < 3; ++k) gm[k] = lanes_max<32>(gm[k]);
         if (hl == 0)
           for (int k = 0; k < 3; ++k) g_gm[g * 3 + k] = gm[k];
       }
@@ -1154,7 +1138,7 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
         if (has_box && box_shared) {
           lo2 = *reinterpret_cast<const double2*>(pb.lb + i);
           up2 = *reinterpret_cast<const double2*>(pb.ub + i);
-          rb2 = double2{crho(lo2.x, up2.x, rho, s), crho(lo2.y, up2.y, rho, s)};
+          rb2 = double2{row_rho(lo2.x, up2.x, rho, s), row_rho(lo2.y, up2.y, rho, s)};
         }
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
@@ -1167,7 +1151,7 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
           if (has_box && !box_shared) {
             lo = *reinterpret_cast<const double2*>(pb.lb + (int64_t)bm * pb.box_stride + i);
             up = *reinterpret_cast<const double2*>(pb.ub + (int64_t)bm * pb.box_stride + i);
-            rb = double2{crho(lo.x, up.x, rho, s), crho(lo.y, up.y, rho, s)};
+            rb = double2{row_rho(lo.x, up.x, rho, s), row_rho(lo.y, up.y, rho, s)};
           }
           double* R_m = st.work + (int64_t)bm * st.work_stride + ld + i;
           double* x_m = st.x + (int64_t)bm * ld + i;
@@ -1236,9 +1220,8 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
             zn_o = zi;
             yn_o = yi;
             if (has_box) {
-              const double zh = alpha * xt + (1.0 - alpha) * zi;
-              const double zn = fmin(fmax(zh + yi / rbi, loi), upi);
-              const double yn = yi + rbi * (zh - zn);
+              const RowStep rs = row_step(xt, zi, yi, rbi, loi, upi, alpha);
+              const double zn = rs.zn, yn = rs.yn;
               zn_o = zn;
               yn_o = yn;
               cty = yn;
@@ -1266,6 +1249,7 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
         }
       }
       // reduce over the 16 lanes of each date (lanes kq * 16 + 0..15), then one slot per wave
+      // (not lanes_sum<16>: narrowest offset first, another summation order for muv)
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
 #pragma unroll
@@ -1305,17 +1289,14 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
       // mu_i (rhs_i / d) and carries a NaN iterate even where mu = 0 (0 * NaN = NaN), so a
       // non-finite iterate cannot pass as converged: it fails the date loudly
       const bool finite = isfinite(muv);
-      const double eps_p = s.eps_abs + s.eps_rel * fmax(mv[1], mv[2]);
-      const double eps_d = s.eps_abs + s.eps_rel * fmax(mv[4], fmax(mv[5], mv[6]));
+      const double eps_p = eps_prim(mv, s), eps_d = eps_dual(mv, s);
       double rn = 0.0;   // this date's rho request (0: none)
       if (!finite) {
         stat = PQ_NON_CONVEX;
       } else if (it >= s.min_iter && mv[0] <= eps_p && mv[3] <= eps_d) {
         stat = PQ_SOLVED;
       } else if (s.adapt_interval > 0 && it % s.adapt_interval == 0) {
-        const double rp = mv[0] / (fmax(mv[1], mv[2]) + 1e-30);
-        const double rd = mv[3] / (fmax(mv[4], fmax(mv[5], mv[6])) + 1e-30);
-        rn = fmin(fmax(rho * sqrt(rp / (rd + 1e-30)), s.rho_min), s.rho_max);
+        rn = rho_request(mv, rho, s);
       }
       if (stat == PQ_UNSOLVED && it >= s.max_iter) stat = PQ_MAX_ITER;
       g_it[g] = it;

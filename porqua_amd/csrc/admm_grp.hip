@@ -18,7 +18,7 @@
 //
 // Replaces qpsolvers.solve_problem (src/qp_problems.py:211-214) for the batched backtest;
 // the iterates are those of pq_admm_lr_batched up to summation order.
-#include "common.h"
+#include "admm_dev.h"
 #include "capi_util.h"
 
 namespace pq {
@@ -33,24 +33,6 @@ constexpr int UMAXG = 320;   // union rows per group
 // dot products -- group-cap constraints, e.g. 20 sector rows).
 constexpr int MGG_SMALL = 8, MGR_SMALL = 4;
 constexpr int MGG_BIG = 32;
-
-__device__ __forceinline__ double grho(double l, double u, double rho, const pq_settings& s) {
-  if (l == u) return rho * s.eq_scale;
-  if (isinf(l) && isinf(u)) return s.rho_min;
-  return rho;
-}
-
-// reductions over the 32 lanes of a half-wave (xor offsets < 32 stay inside the half)
-__device__ __forceinline__ double hsum(double v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double hmax(double v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 #ifdef PQ_PROFILE
 #define GSTAMP(k)                                                 \
@@ -130,7 +112,7 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
       g_sps[g] = sqrt(fmax(ps, 0.0));
       g_pd[g] = pb.p_diag ? pb.p_diag[b] : 0.0;
       if (FUSE) {   // uniform box rho (host-checked): D = sigma + p_diag + rho_box
-        const double rb = has_box ? grho(pb.lb[(int64_t)b * pb.box_stride], pb.ub[(int64_t)b * pb.box_stride],
+        const double rb = has_box ? row_rho(pb.lb[(int64_t)b * pb.box_stride], pb.ub[(int64_t)b * pb.box_stride],
                                          st.rho[b], s) : 0.0;
         g_rb[g] = rb;
         g_dinv[g] = 1.0 / (sigma + g_pd[g] + rb);
@@ -147,7 +129,7 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
       yg = st.y[(int64_t)b * st.m_ld + r];
       lgv = pb.lg[(int64_t)b * pb.g_stride + r];
       ugv = pb.ug[(int64_t)b * pb.g_stride + r];
-      rg = grho(lgv, ugv, st.rho[b], s);
+      rg = row_rho(lgv, ugv, st.rho[b], s);
     }
     g_zg[e] = zg;
     g_yg[e] = yg;
@@ -186,7 +168,7 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
     if (hl < mg) g_wg[g * MGG + hl] = g_rg[g * MGG + hl] * g_zg[g * MGG + hl] - g_yg[g * MGG + hl];
     double muv = 0.0;
     for (int i = hl; i < n; i += 32) {
-      const double rb = has_box ? grho(lo_h[i], up_h[i], rho, s) : 0.0;
+      const double rb = has_box ? row_rho(lo_h[i], up_h[i], rho, s) : 0.0;
       double rr = sigma * x_h[i] - q_h[i];
       if (has_box) rr += rb * zb_h[i] - yb_h[i];
       for (int r = 0; r < mg; ++r) rr += Cg_h[(int64_t)r * ld + i] * g_wg[g * MGG + r];
@@ -196,11 +178,11 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
       if (mu_h) muv = fma(mu_h[i], v, muv);
     }
     for (int i = n + hl; i < ld; i += 32) V_h[i] = 0.0;
-    muv = hsum(muv);
+    muv = lanes_sum<32>(muv);
     for (int r = 0; r < mg; ++r) {   // Cg . V (each lane re-reads its own V entries)
       double a = 0.0;
       for (int i = hl; i < n; i += 32) a = fma(Cg_h[(int64_t)r * ld + i], V_h[i], a);
-      a = hsum(a);
+      a = lanes_sum<32>(a);
       if (hl == 0) g_cgv[g * MGG + r] = a;
     }
     if (hl == 0) g_muv[g] = muv;
@@ -209,7 +191,7 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
         double a = 0.0;
         if (mu_h)
           for (int i = hl; i < n; i += 32) a = fma(Cg_h[(int64_t)r * ld + i], mu_h[i], a);
-        a = hsum(a);
+        a = lanes_sum<32>(a);
         if (hl == 0) g_cmu[g * MGG + r] = a;
       }
     }
@@ -221,7 +203,7 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
     for (int r = 0; r < mg; ++r) {
       double a = 0.0;
       for (int i = hl; i < n; i += 32) a = fma(Cg_h[(int64_t)r * ld + i], x_h[i], a);
-      a = hsum(a);
+      a = lanes_sum<32>(a);
       if (hl == 0) g_cgx[hg * MGG + r] = a;
     }
     next_rhs(hg);
@@ -477,7 +459,7 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
   #pragma unroll 2
         for (int i = hl; i < n; i += 32) {
           double corr = X_h[i] - (mu_h ? su * mu_h[i] : 0.0);
-          const double rb = has_box ? grho(lo_h[i], up_h[i], rho, s) : 0.0;
+          const double rb = has_box ? row_rho(lo_h[i], up_h[i], rho, s) : 0.0;
           double cgi[MGRA];
           if constexpr (MGR > 0) {
   #pragma unroll
@@ -499,14 +481,14 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
   #pragma unroll
           for (int r = 0; r < MGR; ++r) {
             if (r >= mg) break;
-            const double a = hsum(ztp[r]);
+            const double a = lanes_sum<32>(ztp[r]);
             if (hl == 0) g_zt[g * MGG + r] = a;
           }
         } else {   // each lane re-reads the x~ entries it wrote
           for (int r = 0; r < mg; ++r) {
             double a = 0.0;
             for (int i = hl; i < n; i += 32) a = fma(Cg_h[(int64_t)r * ld + i], X_h[i], a);
-            a = hsum(a);
+            a = lanes_sum<32>(a);
             if (hl == 0) g_zt[g * MGG + r] = a;
           }
         }
@@ -516,7 +498,7 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
         for (int r = 0; r < mg; ++r) {
           double a = 0.0;
           for (int u = hl; u < Ug; u += 32) a = fma(pc[(int64_t)(s_urow[u] - r0) * ldpc + r], UT[u * GMAX + g], a);
-          a = hsum(a);
+          a = lanes_sum<32>(a);
           double cw = 0.0;
           for (int r2 = 0; r2 < mg; ++r2) cw = fma(cc[r * mg + r2], g_cw[g * MGG + r2], cw);
           if (hl == 0) g_zt[g * MGG + r] = g_cgv[g * MGG + r] - dinv * (a - su * g_cmu[g * MGG + r] + cw);
@@ -526,9 +508,8 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
       if (hl < mg) {   // general row hl: z, y, Cx (lane-owned); R z - y for the next rhs
         const int e = g * MGG + hl;
         const double rg = g_rg[e], zt = g_zt[e];
-        const double zh = alpha * zt + (1.0 - alpha) * g_zg[e];
-        const double zn = fmin(fmax(zh + g_yg[e] / rg, g_lg[e]), g_ug[e]);
-        const double yn = g_yg[e] + rg * (zh - zn);
+        const RowStep rs = row_step(zt, g_zg[e], g_yg[e], rg, g_lg[e], g_ug[e], alpha);
+        const double zn = rs.zn, yn = rs.yn;
         const double cx = alpha * zt + (1.0 - alpha) * g_cgx[e];
         mv[0] = fabs(cx - zn);
         mv[1] = fabs(cx);
@@ -545,7 +526,7 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
       for (int r = 0; r < MGRA; ++r) cvp[r] = 0.0;
 #pragma unroll 2
       for (int i = hl; i < n; i += 32) {
-        const double rb = has_box ? grho(lo_h[i], up_h[i], rho, s) : 0.0;
+        const double rb = has_box ? row_rho(lo_h[i], up_h[i], rho, s) : 0.0;
         const double rr0 = R_h[i];
         double xt, pxt, cgy = 0.0, cgw = 0.0, cgi[MGRA];
         if constexpr (MGR == 0) {   // many rows: each Cg entry of asset i read once for all four sums
@@ -596,9 +577,8 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
         double rr = sigma * xn - qi + cgw;
         double cty = 0.0;
         if (has_box) {
-          const double zh = alpha * xt + (1.0 - alpha) * zb_h[i];
-          const double zn = fmin(fmax(zh + yb_h[i] / rb, lo_h[i]), up_h[i]);
-          const double yn = yb_h[i] + rb * (zh - zn);
+          const RowStep rs = row_step(xt, zb_h[i], yb_h[i], rb, lo_h[i], up_h[i], alpha);
+          const double zn = rs.zn, yn = rs.yn;
           zb_h[i] = zn;
           yb_h[i] = yn;
           cty = yn;
@@ -624,13 +604,13 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
         }
       }
 #pragma unroll
-      for (int e = 0; e < 7; ++e) mv[e] = hmax(mv[e]);
-      muv = hsum(muv);
+      for (int e = 0; e < 7; ++e) mv[e] = lanes_max<32>(mv[e]);
+      muv = lanes_sum<32>(muv);
       if constexpr (MGR > 0) {
 #pragma unroll
         for (int r = 0; r < MGR; ++r) {
           if (r >= mg) break;
-          cvp[r] = hsum(cvp[r]);
+          cvp[r] = lanes_sum<32>(cvp[r]);
         }
       } else {   // Cg V: written straight to the date's slots (read only by the next symv);
                  // four rows per pass over the date's vector (FUSE: V = rhs / c is not stored)
@@ -646,31 +626,15 @@ __global__ __launch_bounds__(GT) void k_admm_grp(pq_lowrank lr, pq_problem pb, p
           }
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const double v = hsum(a[e]);
+            const double v = lanes_sum<32>(a[e]);
             if (hl == 0 && q0 + e < mg) g_cgv[g * MGG + q0 + e] = v;
           }
         }
       }
       const int it = g_it[g] + 1;
-      int stat = PQ_UNSOLVED;
-      const double eps_p = s.eps_abs + s.eps_rel * fmax(mv[1], mv[2]);
-      const double eps_d = s.eps_abs + s.eps_rel * fmax(mv[4], fmax(mv[5], mv[6]));
-      double rnew = rho;
-      if (it >= s.min_iter && mv[0] <= eps_p && mv[3] <= eps_d) {
-        stat = PQ_SOLVED;
-      } else if (s.adapt_interval > 0 && it % s.adapt_interval == 0 && it < s.max_iter) {
-        // (not at max_iter itself: a date left NEED_REFACTOR there was resumed after the
-        // refactorisation for one iteration beyond max_iter)
-        const double rp = mv[0] / (fmax(mv[1], mv[2]) + 1e-30);
-        const double rd = mv[3] / (fmax(mv[4], fmax(mv[5], mv[6])) + 1e-30);
-        double rn = rho * sqrt(rp / (rd + 1e-30));
-        rn = fmin(fmax(rn, s.rho_min), s.rho_max);
-        if (rn > rho * s.adapt_tol || rn < rho / s.adapt_tol) {
-          rnew = rn;
-          stat = PQ_NEED_REFACTOR;
-        }
-      }
-      if (stat == PQ_UNSOLVED && it >= s.max_iter) stat = PQ_MAX_ITER;
+      const Verdict vd = verdict(mv, it, rho, s);
+      const int stat = vd.status;
+      const double rnew = vd.rho;
       const bool cont = (stat == PQ_UNSOLVED) && it < g_end[g];
       if (hl == 0) {
         g_it[g] = it;

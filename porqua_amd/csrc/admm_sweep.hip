@@ -24,7 +24,7 @@
 // stopping rule, adaptive rho (NEED_REFACTOR), min_iter / max_iter and per-call iteration
 // budget.  Replaces qpsolvers.solve_problem (src/qp_problems.py:211-214) for the sweep's
 // batched solve (src/optimization.py:168-174 per risk aversion).
-#include "common.h"
+#include "admm_dev.h"
 #include "capi_util.h"
 
 // (experiment builds only) PQ_SW_X = 1: no state stores in the updates; 4: no pass-2 MFMA;
@@ -76,24 +76,6 @@ enum {
 constexpr int SC_N = 5 + 5 * SW_MG;
 enum { C_DINV = 0, C_RB, C_SU, C_ACT, C_CW = 4, C_RGZ = 8, C_YG = 12, C_WG = 16, C_WGP = 20, C_RBI = 24 };
 
-__device__ __forceinline__ double sw_grho(double l, double u, double rho, const pq_settings& s) {
-  if (l == u) return rho * s.eq_scale;
-  if (isinf(l) && isinf(u)) return s.rho_min;
-  return rho;
-}
-
-// reductions over the 16 lanes of a row (xor offsets < 16 stay inside it)
-__device__ __forceinline__ double qsum16(double v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double qmax16(double v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // ---- per-problem setup (one thread per problem slot of every group) ------------------------
 __global__ __launch_bounds__(256) void k_sw_setup(pq_lowrank lr, pq_problem pb, pq_state st, pq_settings s,
                                                   const int32_t* gdates, int ngroups, double* SR,
@@ -108,7 +90,7 @@ __global__ __launch_bounds__(256) void k_sw_setup(pq_lowrank lr, pq_problem pb, 
   const int stt = st.status[b];
   const int act = (stt == PQ_UNSOLVED || stt == PQ_NEED_REFACTOR);
   const double rho = st.rho[b];
-  const double rb = pb.lb ? sw_grho(pb.lb[(int64_t)b * pb.box_stride], pb.ub[(int64_t)b * pb.box_stride], rho, s)
+  const double rb = pb.lb ? row_rho(pb.lb[(int64_t)b * pb.box_stride], pb.ub[(int64_t)b * pb.box_stride], rho, s)
                           : 0.0;
   const double pd = pb.p_diag ? pb.p_diag[b] : 0.0;
   const double ps = (pb.p_scale ? pb.p_scale[b] : 1.0) * (lr.w_scale ? lr.w_scale[b] : 1.0);
@@ -131,7 +113,7 @@ __global__ __launch_bounds__(256) void k_sw_setup(pq_lowrank lr, pq_problem pb, 
       yg = st.y[(int64_t)b * st.m_ld + r];
       lgv = pb.lg[(int64_t)b * pb.g_stride + r];
       ugv = pb.ug[(int64_t)b * pb.g_stride + r];
-      rg = sw_grho(lgv, ugv, rho, s);
+      rg = row_rho(lgv, ugv, rho, s);
     }
     R[S_ZG + r] = zg;
     R[S_YG + r] = yg;
@@ -395,6 +377,7 @@ __global__ __launch_bounds__(SW_T) void k_sw_pass(pq_lowrank lr, pq_problem pb, 
             const double xn = alpha * xt + (1.0 - alpha) * x;
             const double pxn = alpha * pxt + (1.0 - alpha) * px;
             double rr = sigma * xn - qi + cgw;
+            // (not row_step: the projection multiplies by the stored 1 / rho_box, one fma, no division)
             const double zh = alpha * xt + (1.0 - alpha) * zb;
             const double zn = fmin(fmax(fma(yb, sc[C_RBI], zh), lo), up);
             const double yn = yb + rb * (zh - zn);
@@ -491,21 +474,21 @@ __global__ __launch_bounds__(SW_T) void k_sw_pass(pq_lowrank lr, pq_problem pb, 
       for (int k = 0; k < RP_N; ++k) o[k] = 0.0;
       const double* ra = racc_l + e * SW_T + t;
       if constexpr (MODE == 1) {   // (slots 2 and 5 stay 0: merged into 1 and 4)
-        o[0] = qmax16(ra[0]);
-        o[1] = qmax16(ra[2 * SW_T]);
-        o[3] = qmax16(ra[4 * SW_T]);
-        o[4] = qmax16(ra[6 * SW_T]);
-        o[6] = qsum16(ra[8 * SW_T]);
+        o[0] = lanes_max<16>(ra[0]);
+        o[1] = lanes_max<16>(ra[2 * SW_T]);
+        o[3] = lanes_max<16>(ra[4 * SW_T]);
+        o[4] = lanes_max<16>(ra[6 * SW_T]);
+        o[6] = lanes_sum<16>(ra[8 * SW_T]);
 #pragma unroll
-        for (int r = 0; r < MGR; ++r) o[8 + r] = qsum16(rcg[e][r]);
+        for (int r = 0; r < MGR; ++r) o[8 + r] = lanes_sum<16>(rcg[e][r]);
       } else {
-        o[0] = qmax16(ra[0]);
-        o[6] = qsum16(ra[8 * SW_T]);
+        o[0] = lanes_max<16>(ra[0]);
+        o[6] = lanes_sum<16>(ra[8 * SW_T]);
 #pragma unroll
         for (int r = 0; r < MGR; ++r) {
-          o[1 + r] = qsum16(rcm[e][r]);
-          o[8 + r] = qsum16(rcg[e][r]);
-          o[12 + r] = qsum16(rcx[e][r]);
+          o[1 + r] = lanes_sum<16>(rcm[e][r]);
+          o[8 + r] = lanes_sum<16>(rcg[e][r]);
+          o[12 + r] = lanes_sum<16>(rcx[e][r]);
         }
       }
       if (ui == 0) {
@@ -617,34 +600,14 @@ __global__ __launch_bounds__(SW_MT) void k_sw_mid(pq_lowrank lr, pq_problem pb, 
   if (t == 0) {
     int cont = 1;
     if constexpr (MODE == 1) {
-      const double mv0 = fmax(red[0], sr[S_RMV + 0]), mv1 = fmax(red[1], sr[S_RMV + 1]),
-                   mv2 = fmax(red[2], sr[S_RMV + 2]);
-      const double mv3 = red[3], mv4 = red[4], mv5 = red[5], mv6 = sr[S_QMAX];
-      const double rho = sr[S_RHO];
+      const double mv[7] = {fmax(red[0], sr[S_RMV + 0]), fmax(red[1], sr[S_RMV + 1]), fmax(red[2], sr[S_RMV + 2]),
+                            red[3], red[4], red[5], sr[S_QMAX]};
       const int it = (int)sr[S_IT] + 1;
-      int stat = PQ_UNSOLVED;
-      const double eps_p = s.eps_abs + s.eps_rel * fmax(mv1, mv2);
-      const double eps_d = s.eps_abs + s.eps_rel * fmax(mv4, fmax(mv5, mv6));
-      double rnew = rho;
-      if (it >= s.min_iter && mv0 <= eps_p && mv3 <= eps_d) {
-        stat = PQ_SOLVED;
-      } else if (s.adapt_interval > 0 && it % s.adapt_interval == 0 && it < s.max_iter) {
-        // (not at max_iter itself: a problem left NEED_REFACTOR there was resumed after the
-        // refactorisation for one iteration beyond max_iter)
-        const double rp = mv0 / (fmax(mv1, mv2) + 1e-30);
-        const double rd = mv3 / (fmax(mv4, fmax(mv5, mv6)) + 1e-30);
-        double rn = rho * sqrt(rp / (rd + 1e-30));
-        rn = fmin(fmax(rn, s.rho_min), s.rho_max);
-        if (rn > rho * s.adapt_tol || rn < rho / s.adapt_tol) {
-          rnew = rn;
-          stat = PQ_NEED_REFACTOR;
-        }
-      }
-      if (stat == PQ_UNSOLVED && it >= s.max_iter) stat = PQ_MAX_ITER;
-      cont = (stat == PQ_UNSOLVED) && it < (int)sr[S_END];
+      const Verdict vd = verdict(mv, it, sr[S_RHO], s);
+      cont = (vd.status == PQ_UNSOLVED) && it < (int)sr[S_END];
       R[S_IT] = it;
-      R[S_RHO] = rnew;
-      R[S_STAT] = stat;
+      R[S_RHO] = vd.rho;
+      R[S_STAT] = vd.status;
       R[S_ACT] = cont;
       R[S_MUV] = red[6];
 #pragma unroll
@@ -774,9 +737,8 @@ __global__ __launch_bounds__(SW_MT) void k_sw_mid(pq_lowrank lr, pq_problem pb, 
       for (int r2 = 0; r2 < mg; ++r2) cwr = fma(cc[r * mg + r2], cw[r2], cwr);
       const double zt = sr[S_CGV + r] - dinv * (a - sut * sr[S_CMU + r] + cwr);
       const double rg = sr[S_RG + r], zg = sr[S_ZG + r], yg = sr[S_YG + r];
-      const double zh = s.alpha * zt + (1.0 - s.alpha) * zg;
-      const double zn = fmin(fmax(zh + yg / rg, sr[S_LG + r]), sr[S_UG + r]);
-      const double yn = yg + rg * (zh - zn);
+      const RowStep rs = row_step(zt, zg, yg, rg, sr[S_LG + r], sr[S_UG + r], s.alpha);
+      const double zn = rs.zn, yn = rs.yn;
       const double cx = s.alpha * zt + (1.0 - s.alpha) * sr[S_CGX + r];
       m0 = fmax(m0, fabs(cx - zn));
       m1 = fmax(m1, fabs(cx));

@@ -1,7 +1,7 @@
 // Workgroup-level blocked Cholesky on FP64 MFMA (header-only, shared by K2 and K4).
 // See chol.hip for the algorithm description.
 #pragma once
-#include "common.h"
+#include "admm_dev.h"
 
 namespace pq {
 
@@ -238,22 +238,15 @@ struct FormCtx {
   double rho, rho_min, eq_scale;
 };
 
-__device__ __forceinline__ double rho_for(double l, double u, double rho, double rho_min,
-                                          double eq_scale) {
-  if (l == u) return rho * eq_scale;
-  if (isinf(l) && isinf(u)) return rho_min;
-  return rho;
-}
-
 __device__ __forceinline__ double form_elem(const FormCtx& f, int gi, int gj) {
   if (gi >= f.n || gj >= f.n) return gi == gj ? 1.0 : 0.0;
   double v = f.ps * f.P[(int64_t)gi * f.ld + gj];
   for (int r = 0; r < f.mg; ++r)
-    v += rho_for(f.lg[r], f.ug[r], f.rho, f.rho_min, f.eq_scale) * f.Cg[(int64_t)r * f.ld + gi] *
+    v += row_rho(f.lg[r], f.ug[r], f.rho, f.rho_min, f.eq_scale) * f.Cg[(int64_t)r * f.ld + gi] *
          f.Cg[(int64_t)r * f.ld + gj];
   if (gi == gj) {
     v += f.pd + f.sigma;
-    if (f.lb != nullptr) v += rho_for(f.lb[gi], f.ub[gi], f.rho, f.rho_min, f.eq_scale);
+    if (f.lb != nullptr) v += row_rho(f.lb[gi], f.ub[gi], f.rho, f.rho_min, f.eq_scale);
   }
   return v;
 }

@@ -300,17 +300,26 @@ __device__ __forceinline__ int xcd_slot(int g, int N) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (g >> 3);
 }
 
+// ---- lane-group reductions: an xor butterfly over aligned groups of W lanes (offsets < W
+// stay inside the group; widest offset first); every lane ends with its group's result -----
+template <int W>
+__device__ __forceinline__ double lanes_sum(double v) {
+  static_assert(W >= 2 && W <= 64 && (W & (W - 1)) == 0, "a power of two, at most the wave");
+#pragma unroll
+  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+template <int W>
+__device__ __forceinline__ double lanes_max(double v) {
+  static_assert(W >= 2 && W <= 64 && (W & (W - 1)) == 0, "a power of two, at most the wave");
+#pragma unroll
+  for (int o = W / 2; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_sum(double v) { return lanes_sum<64>(v); }
+__device__ __forceinline__ double wave_max(double v) { return lanes_max<64>(v); }
+
 // ---- workgroup reductions (any block size that is a multiple of 64, <= 1024) ----------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
 // red must hold >= 16 doubles of LDS.  Result broadcast to every thread.
 __device__ __forceinline__ double block_sum(double v, double* red) {
   v = wave_sum(v);

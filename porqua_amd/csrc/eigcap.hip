@@ -23,19 +23,13 @@
 // Replaces the per-(date, lambda) factorisation behind qpsolvers.solve_problem
 // (src/qp_problems.py:211-214) for MeanVariance objectives P = 2 lambda Sigma_d
 // (src/optimization.py:168-174) swept over lambda.
-#include "common.h"
+#include "admm_dev.h"
 #include "capi_util.h"
 
 namespace pq {
 
 constexpr int EMG = 4;        // general rows supported (budget + up to 3 more)
 constexpr int EKMAX = 512;    // k_ld limit (lowrank_shape_ok)
-
-__device__ __forceinline__ double eig_rho(double l, double u, double rho, const pq_settings& s) {
-  if (l == u) return rho * s.eq_scale;
-  if (isinf(l) && isinf(u)) return s.rho_min;
-  return rho;
-}
 
 struct EigScal {
   double ps, c;
@@ -48,7 +42,7 @@ __device__ __forceinline__ EigScal eig_scal(const pq_lowrank& lr, const pq_probl
   const double pd = pb.p_diag ? pb.p_diag[b] : 0.0;
   const double* lb = pb.lb ? pb.lb + (int64_t)b * pb.box_stride : nullptr;
   const double* ub = pb.ub ? pb.ub + (int64_t)b * pb.box_stride : nullptr;
-  return EigScal{ps, s.sigma + pd + (lb ? eig_rho(lb[0], ub[0], rho, s) : 0.0)};
+  return EigScal{ps, s.sigma + pd + (lb ? row_rho(lb[0], ub[0], rho, s) : 0.0)};
 }
 
 // ---- per problem: Schur complement, Q, Q S^-1, border rows, padding ---------------------
@@ -68,7 +62,7 @@ __global__ __launch_bounds__(256) void k_eig_border(pq_lowrank lr, pq_problem pb
   const EigScal sc = eig_scal(lr, pb, rho_all, s, b);
   const double a1 = sc.ps / sc.c;
   if (t < mg)
-    s_sr[t] = sqrt(eig_rho(pb.lg[(int64_t)b * pb.g_stride + t], pb.ug[(int64_t)b * pb.g_stride + t],
+    s_sr[t] = sqrt(row_rho(pb.lg[(int64_t)b * pb.g_stride + t], pb.ug[(int64_t)b * pb.g_stride + t],
                            rho_all[b], s));
   const double* ev = evals + (int64_t)d * k_ld;
   const double* Wh = What + (int64_t)d * k_ld * EMG;

@@ -8,16 +8,10 @@
 // from the panel through the date's row list and scaled / centred / weighted by
 // 1/sqrt(D_c) while they are staged into LDS.  2 k^2 n flop per date (k ~ 253, n = 1000:
 // 1.3e8) instead of the n^3 of the dense KKT factorisation.
-#include "common.h"
+#include "admm_dev.h"
 #include "capi_util.h"
 
 namespace pq {
-
-__device__ __forceinline__ double lr_rho(double l, double u, double rho, const pq_settings& s) {
-  if (l == u) return rho * s.eq_scale;
-  if (isinf(l) && isinf(u)) return s.rho_min;
-  return rho;
-}
 
 struct URow {
   const double* src;   // nullptr: zero row
@@ -39,7 +33,7 @@ __device__ __forceinline__ URow urow(const pq_lowrank& lr, const pq_problem& pb,
     const int k = gi - lr.tmax;
     const double l = pb.lg[(int64_t)b * pb.g_stride + k], u = pb.ug[(int64_t)b * pb.g_stride + k];
     r.src = pb.Cg + (int64_t)b * pb.Cg_stride + (int64_t)k * pb.ld;
-    r.scale = sqrt(lr_rho(l, u, rho, s));
+    r.scale = sqrt(row_rho(l, u, rho, s));
   }
   return r;
 }
@@ -94,7 +88,7 @@ __global__ __launch_bounds__(256) void k_lr_gram(pq_lowrank lr, pq_problem pb, c
     if (threadIdx.x < KC) {
       const int c = c0 + threadIdx.x;
       double d = s.sigma + pd;
-      if (lb && c < n) d += lr_rho(lb[c], ub[c], rho, s);
+      if (lb && c < n) d += row_rho(lb[c], ub[c], rho, s);
       dst[threadIdx.x] = c < n ? 1.0 / sqrt(d) : 0.0;
     }
   };
@@ -288,9 +282,9 @@ __global__ __launch_bounds__(256) void k_lr_cap_band(pq_lowrank lr, pq_problem p
   const double pd = pb.p_diag ? pb.p_diag[b] : 0.0;
   const double* lb = pb.lb ? pb.lb + (int64_t)b * pb.box_stride : nullptr;
   const double* ub = pb.ub ? pb.ub + (int64_t)b * pb.box_stride : nullptr;
-  const double c = s.sigma + pd + (lb ? lr_rho(lb[0], ub[0], rho, s) : 0.0);   // uniform D (host-checked)
+  const double c = s.sigma + pd + (lb ? row_rho(lb[0], ub[0], rho, s) : 0.0);   // uniform D (host-checked)
   const double a1 = ps / c, a2 = sqrt(fmax(ps, 0.0)) / c;
-  if (t < mg) s_sr[t] = sqrt(lr_rho(pb.lg[(int64_t)b * pb.g_stride + t], pb.ug[(int64_t)b * pb.g_stride + t], rho, s));
+  if (t < mg) s_sr[t] = sqrt(row_rho(pb.lg[(int64_t)b * pb.g_stride + t], pb.ug[(int64_t)b * pb.g_stride + t], rho, s));
   __syncthreads();
   double* M = M_all + (int64_t)b * M_stride;
   for (int i = w; i < k_ld; i += 4) {

@@ -1006,11 +1006,6 @@ __global__ __launch_bounds__(FT) void k_pg_form_grp_big(pq_lowrank lr, pq_proble
 // ---------------------------------------------------------------------------------------
 constexpr int WMA = 8;   // active general rows handled by the solve (more: fallback)
 
-__device__ __forceinline__ double sum16(double v) {   // over the 16 lanes of a DPP row
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ double sum4(double v) {
   v += __shfl_xor(v, 1, 64);
   v += __shfl_xor(v, 2, 64);
@@ -1132,7 +1127,7 @@ __device__ __forceinline__ void b_fwd(const double* Lp, int k, double* y, double
     for (int e = t; e < 256; e += T) {
       const int i = e >> 4, m = e & 15;
       double v = (i < nb && m <= i) ? Lp[pk(p0 + i, p0 + m)] * y[p0 + m] : 0.0;
-      v = sum16(v);
+      v = lanes_sum<16>(v);
       if (m == 0 && i < nb) yo[p0 + i] = v;
     }
     __syncthreads();
@@ -1165,7 +1160,7 @@ __device__ __forceinline__ void b_bwd(const double* Lp, int k, double* y, double
     for (int e = t; e < 256; e += T) {
       const int i = e >> 4, m = e & 15;
       double v = (i < nb && m >= i && m < nb) ? Lp[pk(p0 + m, p0 + i)] * y[p0 + m] : 0.0;
-      v = sum16(v);
+      v = lanes_sum<16>(v);
       if (m == 0 && i < nb) xo[p0 + i] = v;
     }
     __syncthreads();
@@ -1817,17 +1812,6 @@ constexpr int QNW = QT / 64;
 constexpr int QG = 16;     // dates per group (MFMA N)
 constexpr int QU = 320;    // union rows per group
 
-__device__ __forceinline__ double hsum32(double v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double hmax32(double v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // The two window passes of a group run split over PQ_PG_SPLIT workgroups each (the union
 // rows' columns divided between them), so a late round with few pending groups is not one
 // latency-bound workgroup per group:
@@ -1909,7 +1893,7 @@ __global__ __launch_bounds__(QT) void k_pg_passA(pq_lowrank lr, pq_problem pb, p
     double a = 0.0;
     if (mu)
       for (int i = k_lo + hl; i < k_hi; i += 32) a = fma(mu[i], v[i], a);
-    a = hsum32(a);
+    a = lanes_sum<32>(a);
     if (hl == 0) Mp[hg] = a;
   } else if (hg < QG && hl == 0) {
     Mp[hg] = 0.0;

@@ -39,12 +39,6 @@ constexpr int YMG = PG_WG_MAX;   // general rows
 constexpr int YCH = 64;          // Woodbury correction rank U - T + 1
 constexpr int YNP = 3;           // per-date partials of a pass-2 epilogue
 
-__device__ __forceinline__ double ysum32(double v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(YT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_pgw(
     pq_lowrank lr, pq_problem pb, pq_state st, pq_gcap gc, double* rec, pq_settings s, const double* pc,
     int64_t ldpc, int r0, const double* cc, const int32_t* nzr, const double* nzv, int nzmax, double* wscr,
@@ -158,7 +152,7 @@ __global__ __launch_bounds__(YT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
       if (bid >= 0) {
         const double* cr = pb.Cg + (int64_t)bid * ld;
         for (int i = hl; i < n; i += 32) v = fma(cr[i], mu[i], v);
-        v = ysum32(v);
+        v = lanes_sum<32>(v);
       } else {
         v = mu[-1 - bid];
       }
@@ -171,7 +165,7 @@ __global__ __launch_bounds__(YT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
       const double* mu = lr.mu + (int64_t)(d0 + g) * lr.mu_stride;
       const double* x = st.work + (int64_t)(d0 + g) * st.work_stride;   // PGWork xs
       for (int i = hl; i < n; i += 32) v = fma(mu[i], x[i], v);
-      v = ysum32(v);
+      v = lanes_sum<32>(v);
     }
     if (hl == 0) g_mux[g] = v;
   }
@@ -301,7 +295,7 @@ __global__ __launch_bounds__(YT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
       double az = 0.0;
       if (centred)
         for (int u = hl; u < U; u += 32) az = fma(A[u], WU[u * YG + m], az);
-      az = ysum32(az);
+      az = lanes_sum<32>(az);
       double sj[2];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -481,7 +475,7 @@ __global__ __launch_bounds__(YT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     const double* ws = wscr + (int64_t)(d0 + g) * wstride;
     double v = 0.0;
     for (int u = hl; u < U; u += 32) v = fma(ws[(int64_t)(YMB + j) * k_ld + u], ws[(int64_t)k * k_ld + u], v);
-    v = ysum32(v);
+    v = lanes_sum<32>(v);
     if (hl == 0) {
       const int bj = g_bid[g * YMB + j], bk = g_bid[g * YMB + k];
       double bb;
@@ -533,7 +527,7 @@ __global__ __launch_bounds__(YT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
       double v = 0.0;
       if (g_run[m])
         for (int u = hl; u < U; u += 32) v += WU[u * YG + m];
-      v = ysum32(v);
+      v = lanes_sum<32>(v);
       if (hl == 0) g_sw[m] = v;
     }
     __syncthreads();
@@ -610,7 +604,7 @@ __global__ __launch_bounds__(YT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
       const double* xb = wscr + (int64_t)(d0 + m) * wstride + (int64_t)(YMB + j) * k_ld;
       double v = 0.0;
       for (int u = hl; u < U; u += 32) v = fma(xb[u], WU[u * YG + m], v);
-      v = ysum32(v);
+      v = lanes_sum<32>(v);
       if (hl == 0) g_dlam[e] = v;
     }
     __syncthreads();

@@ -38,11 +38,6 @@ constexpr int RT_WMA = 8;   // active general rows of the solve (more: fallback)
 
 __device__ constexpr int ti(int I, int J) { return I * (I + 1) / 2 + J; }
 
-__device__ __forceinline__ double sum16r(double v) {   // over the 16 lanes of a row group
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ double sum_g(double v) {    // over the 4 row groups (lanes l ^ 16, l ^ 32)
   v += __shfl_xor(v, 16, 64);
   v += __shfl_xor(v, 32, 64);
@@ -110,7 +105,7 @@ PQ_DEVFN void rt_load(f64x4 (&S)[NB * (NB + 1) / 2], const double* K, int ldk, c
         for (int q = 0; q < 4; ++q) S[ti(I, J)][q] = (I == J && c16 == g + 4 * q) ? 1.0 : 0.0;
     }
 #pragma unroll
-    for (int q = 0; q < 4; ++q) pc[q] = sum16r(pc[q]);   // (A_IJ' x_I)[16J + g + 4q], I > J
+    for (int q = 0; q < 4; ++q) pc[q] = lanes_sum<16>(pc[q]);   // (A_IJ' x_I)[16J + g + 4q], I > J
     if (c16 == 0) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) px[16 * J + g + 4 * q] = pc[q];
@@ -223,7 +218,7 @@ PQ_DEVFN void rt_bwd(const f64x4 (&S)[NB * (NB + 1) / 2], int k, const double* y
       }
       if (J + 1 < nbk) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) a[q] = sum16r(a[q]);   // (sum_I L_IJ' x_I)[g + 4q]
+        for (int q = 0; q < 4; ++q) a[q] = lanes_sum<16>(a[q]);   // (sum_I L_IJ' x_I)[g + 4q]
       }
       if (c16 == 0) {
 #pragma unroll
@@ -232,7 +227,7 @@ PQ_DEVFN void rt_bwd(const f64x4 (&S)[NB * (NB + 1) / 2], int k, const double* y
       __syncthreads();
       const double rr = tv[c16];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) a[q] = sum16r(S[ti(J, J)][q] * rr);   // (L_JJ^-T r)[g + 4q]
+      for (int q = 0; q < 4; ++q) a[q] = lanes_sum<16>(S[ti(J, J)][q] * rr);   // (L_JJ^-T r)[g + 4q]
       if (c16 == 0) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) x[16 * J + g + 4 * q] = a[q];
