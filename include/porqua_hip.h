@@ -615,6 +615,40 @@ int pq_shrink_stats_band(const double* band, int64_t ldo, int32_t r0, int32_t nr
                          int32_t batch, int32_t n, int32_t centred, int32_t kind, double* stats,
                          void* stream);
 
+/* Risk-parity (risk-budgeting, equal risk contribution) portfolios of a batch of dates on the
+ * window form Sigma_b = a[b] Xc'Xc + c[b] I (Xc: date b's window of lr, centred by lr->mu; mu ==
+ * NULL: uncentred; panel, ldp, rows, tlen, tmax, mu, dg are read exactly as the ADMM kernels read
+ * them, w_scale is not used: the per-date scalars a and c carry the estimator -- pearson
+ * (1/(T-1), 0), linear shrinkage c = lambda mean(diag S), Ledoit-Wolf / OAS ((1-delta)/(T-1),
+ * delta mean(diag S)), identity (0, 1)).  Per date, Spinu's convex form
+ *   y* = argmin_{y > 0} 1/2 y' Sigma y - sum_i b_i log y_i,      x[b] = scale y* / sum(y*),
+ * whose optimality condition y_i (Sigma y)_i = b_i says that asset i carries the share b_i of the
+ * portfolio variance, by cyclical coordinate descent (Griveau-Billion, Richard, Roncalli 2013):
+ * in the order i = 0..n-1, from y_i = sqrt(b_i / d_i), with d_i = a dg_i + c and
+ * s_i = (Sigma y)_i - d_i y_i,   y_i <- (-s_i + sqrt(s_i^2 + 4 d_i b_i)) / (2 d_i).  Nothing n x n
+ * is formed: r = Xc y is carried along, 16 assets per step on FP64 MFMA (the same ordered
+ * recurrence in exact arithmetic).  budget: the risk budgets b (b_i > 0; the residual below is
+ * relative to b_i, so they should sum to 1), row stride ldb, ldb = 0: one row shared by all dates.
+ *   stats[b] = { res, sweeps, x' Sigma x, sum(y) },  res = max_i |y_i (Sigma y)_i - b_i| / b_i
+ * of the y that is returned (y = x sum(y) / scale), evaluated with r recomputed from that y.
+ * status[b]: PQ_RP_OK (res <= eps); PQ_RP_MAX_SWEEPS (max_sweeps sweeps done, res > eps: x is the
+ * last iterate, finite, and res is its residual); PQ_RP_BAD_INPUT (x[b] and stats[b] are NaN and
+ * nothing beyond the checks was read: a budget entry <= 0 or non-finite, some d_i <= 0 or
+ * non-finite -- a zero-variance asset without a ridge, a NaN in the window (through dg) --, a or c
+ * negative or non-finite, tlen[b] outside [1, tmax], a negative window row).  max_sweeps = k with
+ * eps = 0 returns the k-th iterate.  The residual is evaluated after a sweep, so a date takes at
+ * least one sweep unless max_sweeps = 0 (which returns the start with its residual).  One
+ * 256-thread workgroup per date: a date never affects another date, and without floating-point
+ * atomics the same input gives the same bits.
+ * 1 <= tmax <= 1024, n >= 1, ldx >= n; x is batch x ldx, stats batch x 4.  The call does not
+ * synchronise; only host-checkable arguments return an error.                              */
+#define PQ_RP_OK 0
+#define PQ_RP_MAX_SWEEPS 1
+#define PQ_RP_BAD_INPUT 2
+int pq_risk_parity_batched(const pq_lowrank* lr, int32_t n, int32_t batch, const double* a, const double* c,
+                           const double* budget, int64_t ldb, double scale, double eps, int32_t max_sweeps,
+                           double* x, int64_t ldx, double* stats, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,10 @@ PQ_PCT_OK, PQ_PCT_EMPTY_BUCKET, PQ_PCT_NAN_SCORE = range(3)
 PQ_PCT_MAX_N = 16384
 PQ_PCT_MAX_BUCKETS = 256
 
+# pq_risk_parity_batched: per-date status and the longest window (include/porqua_hip.h)
+PQ_RP_OK, PQ_RP_MAX_SWEEPS, PQ_RP_BAD_INPUT = range(3)
+PQ_RP_TMAX = 1024
+
 PQ_PG_RECORD = 384                   # doubles per problem of the grouped polish record
 PQ_PG_PASS_SCRATCH = 123537          # doubles per slide group of the split polish window passes
 PQ_PG_PENDING, PQ_PG_DONE, PQ_PG_FALLBACK, PQ_PG_SKIP = range(4)
@@ -228,6 +232,9 @@ _EXPORTS = {
                                c_dp, c_dp, c_dp, c_dp, c_dp, c_dp], c_int32),
     "pq_shrink_stats_band": ([c_dp, c_int64, c_int32, c_int32, c_int32, c_dp, c_int64, c_dp, c_int32, c_int32,
                               c_int32, c_int32, c_int32, c_dp, c_dp], c_int32),
+    "pq_risk_parity_batched": ([ctypes.POINTER(PQLowRank), c_int32, c_int32, c_dp, c_dp, c_dp, c_int64,
+                                ctypes.c_double, ctypes.c_double, c_int32, c_dp, c_int64, c_dp, c_dp, c_dp],
+                               c_int32),
 }
 
 _lib = None

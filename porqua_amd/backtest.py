@@ -19,7 +19,9 @@ loop runs in two phases instead of one serial QP per date:
   C (host): Portfolio objects in date order, ``append_fun`` called per date.
 
 PercentilePortfolios (no QP) batches the same way: phase A, then the scores of every date
-from the device geometric means and one ranking launch (``_run_percentile``).
+from the device geometric means and one ranking launch (``_run_percentile``).  RiskParity (no QP
+either) likewise: phase A, then every date's coordinate descent in one launch
+(``_run_risk_parity``).
 
 Dates are independent in the reference; an ``append_fun`` that mutates
 state read by later dates is not supported in batched mode (set settings['batched'] = False
@@ -348,6 +350,10 @@ class Backtest:
         if hasattr(bs.optimization, "percentile_batch") and _batchable(bs):
             # quantile portfolios: no QP, so no engine solver name; every date ranked in one launch
             if self._run_percentile(bs):
+                return None
+        elif hasattr(bs.optimization, "risk_parity_batch") and _batchable(bs):
+            # risk parity: not a QP either; every date in one coordinate-descent launch
+            if self._run_risk_parity(bs):
                 return None
         elif bs.optimization.params.get("solver_name") in ENGINE_SOLVERS and _batchable(bs):
             if self._run_batched(bs):
@@ -712,6 +718,70 @@ class Backtest:
                 self._after_solve(bs, d)
         # the optimisation's results hold the last date's, as after the serial loop
         opt.results = percentile_results(index, W[-1], bucket[-1], counts[-1])
+        return True
+
+    def _run_risk_parity(self, bs) -> bool:
+        """Batched run of RiskParity: phase A as for the QP path (static selection, panel
+        upload, window rows), every date's risk-parity weights in one launch
+        (``risk_parity_batch``), one copy of weights, stats and status to the host, and phase C.
+        A date that is not PQ_RP_OK raises RuntimeError naming the date and the reason; a panel
+        with missing values raises RuntimeError(RP_NAN_MESSAGE), as the serial loop does.  False:
+        the serial loop has to run (no return-series width).
+
+        Under an initialised process group every rank computes all dates and no collective
+        runs, as for PercentilePortfolios."""
+        import torch
+        from . import _lib, engine
+        from .optimization import RP_NAN_MESSAGE, RP_REASONS
+        rebdates = list(bs.settings["rebdates"])
+        if not rebdates:
+            return False
+        opt = bs.optimization
+        bs.prepare_rebalancing(rebalancing_date=rebdates[0])
+        universe = bs.selection.selected
+        ws = _stage_windows(bs, universe, rebdates)
+        if ws is None:
+            return False
+        _, upload, _, rows, tlen = ws
+        dev = engine.default_device()
+        panel = engine.Panel(upload.result(), None, device=dev)
+        if panel.has_nan:
+            raise RuntimeError(RP_NAN_MESSAGE)
+        stage = BatchStage(panel, rows, tlen, dev)
+        out = opt.risk_parity_batch(stage)
+        if out is None:
+            return False
+        x, stats, status, form = out
+        n = len(universe)
+        # weights, stats and status land in page-locked host memory in one copy (the lazy
+        # Portfolio objects keep views of the weight rows)
+        Ht, H = _pinned_panel(len(rebdates), n + 5)
+        Ht.copy_(torch.cat([x, stats, status.to(torch.float64)[:, None]], 1))
+        W, stats_h, status_h = H[:, :n], H[:, n:n + 4], H[:, n + 4].astype(np.int32)
+        bad = np.flatnonzero(status_h != _lib.PQ_RP_OK)
+        if bad.size:
+            raise RuntimeError(f"RiskParity: rebalancing date {rebdates[bad[0]]}: "
+                               f"{RP_REASONS.get(int(status_h[bad[0]]), 'unknown status')} "
+                               f"(residual {stats_h[bad[0], 0]:.3g} after {stats_h[bad[0], 1]:.0f} sweeps)")
+        self.stats = {"dates": len(rebdates), "solved": len(rebdates), "status": status_h, "path": "risk_parity",
+                      "residual": stats_h[:, 0], "sweeps": stats_h[:, 1].astype(np.int32),
+                      "variance": stats_h[:, 2]}
+        if not bs.settings.get("quiet"):
+            print(f"Solved {len(rebdates)} risk-parity dates on the device")
+        keys = list(universe)
+
+        def results(i):
+            rc = opt.risk_contributions(panel, stage.rows, stage.tlen, form, x, i)
+            return {"weights": dict(zip(keys, W[i].tolist())), "status": True,
+                    "risk_contributions": dict(zip(keys, rc.tolist()))}
+        if bs.settings.get("append_fun") is None:
+            self.strategy.portfolios.extend(Portfolio._from_row(d, keys, W[i]) for i, d in enumerate(rebdates))
+        else:
+            for i, d in enumerate(rebdates):
+                opt.results = results(i)
+                self._after_solve(bs, d)
+        # the optimisation's results hold the last date's, as after the serial loop
+        opt.results = results(len(rebdates) - 1)
         return True
 
     def save(self, filename: str, path: Optional[str] = None) -> None:

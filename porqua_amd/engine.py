@@ -1926,3 +1926,67 @@ def percentile_weights(scores: torch.Tensor, n_percentiles: int, sign: float = -
             _ptr(scores), lds, n, B, float(sign), N, _ptr(plan[0]), _ptr(plan[1]), _ptr(plan[2]),
             _ptr(th), _ptr(bucket), _ptr(counts), _ptr(w), _ptr(status), _stream()), "pq_percentile_batched")
     return w, bucket, counts, th, status
+
+
+def _per_date(v, B: int, dev, what: str):
+    """A per-date FP64 device vector from a scalar or a (B,) tensor / array."""
+    if isinstance(v, torch.Tensor):
+        v = v.to(dev, dtype=F64).flatten()
+    else:
+        v = torch.as_tensor(np.asarray(v, dtype=np.float64), device=dev).flatten()
+    if v.numel() == 1:
+        v = v.expand(B)
+    if v.numel() != B:
+        raise ValueError(f"risk_parity_weights: {what} must be a scalar or one value per date")
+    return v.contiguous()
+
+
+def risk_parity_weights(panel: "Panel", rows, tlen, budgets=None, a=None, c=None, centred: bool = True,
+                        scale: float = 1.0, eps: float = 1e-10, max_sweeps: int = 500, moments=None):
+    """Risk-parity (risk-budgeting) weights of every window (pq_risk_parity_batched): per date
+    x = scale y* / sum(y*) with y* = argmin_{y > 0} 1/2 y' Sigma y - sum_i b_i log y_i, so that
+    asset i carries the share b_i of the portfolio variance, on the window form
+    Sigma = a Xc'Xc + c I (nothing n x n is formed).  ``rows`` / ``tlen``: the device row table
+    (Panel.rows_to_device), at most 1024 rows per window.  ``budgets``: None (equal, 1/n), one
+    (n,) row shared by all dates or (B, n); entries > 0, rows summing to 1 (the residual is
+    relative to b_i).  ``a`` / ``c``: scalars or one value per date; defaults a = 1 / (T_d - 1) (the
+    sample covariance; a one-row window has no sample covariance and is reported as bad input)
+    and c = 0.  ``centred`` False: the uncentred Gram.  ``moments``: (mu, dg) of the windows where
+    the caller already holds them (Panel.window_means / window_sumsq; mu None: uncentred), computed
+    here otherwise.  Returns (x [B, n], stats [B, 4] = res,
+    sweeps, x' Sigma x, sum(y), status [B] int32: _lib.PQ_RP_*), all on the device; a date whose
+    status is PQ_RP_BAD_INPUT has NaN weights, one with PQ_RP_MAX_SWEEPS its last iterate and
+    that iterate's residual.  Does not synchronise."""
+    lib = _lib.load()
+    B, tmax = int(rows.shape[0]), int(rows.shape[1])
+    n, dev = panel.n, panel.device
+    x = torch.empty((B, n), dtype=F64, device=dev)
+    stats = torch.empty((B, 4), dtype=F64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return x, stats, status
+    if not 1 <= tmax <= _lib.PQ_RP_TMAX:
+        raise ValueError(f"risk_parity_weights: windows of up to {tmax} rows (supported: 1..{_lib.PQ_RP_TMAX})")
+    rows = rows.contiguous()   # row pitch tmax, as every window entry point reads the table
+    if budgets is None:
+        bud = torch.full((1, n), 1.0 / n, dtype=F64, device=dev)
+    else:
+        bud = budgets if isinstance(budgets, torch.Tensor) else torch.as_tensor(np.asarray(budgets, dtype=np.float64))
+        bud = bud.to(dev, dtype=F64).reshape(-1, n).contiguous()
+        if bud.shape[0] not in (1, B):
+            raise ValueError("risk_parity_weights: budgets must be (n,) or (B, n)")
+    ldb = 0 if bud.shape[0] == 1 else n
+    if a is None:
+        a = 1.0 / (tlen.to(F64) - 1.0)
+    a = _per_date(a, B, dev, "a")
+    c = _per_date(0.0 if c is None else c, B, dev, "c")
+    if moments is not None:
+        mu, dg = moments
+    else:
+        mu = panel.window_means(rows, tlen) if centred else None
+        dg = panel.window_sumsq(rows, tlen, mu)
+    lr = LowRank(panel, rows, tlen, mu=mu, dg=dg).c_struct()
+    _lib.check(lib.pq_risk_parity_batched(ctypes.byref(lr), n, B, _ptr(a), _ptr(c), _ptr(bud), ldb, float(scale),
+                                          float(eps), int(max_sweeps), _ptr(x), x.stride(0), _ptr(stats),
+                                          _ptr(status), _stream()), "pq_risk_parity_batched")
+    return x, stats, status

@@ -19,7 +19,9 @@ Deliberate differences from the reference ("Reference defects"):
   (src/optimization.py:393); zero weights are +0.0.
 LAD runs on the batched device IPM of porqua_amd/lad.py; PercentilePortfolios (ranking, not
 the QP path) runs on the batched order-statistics kernel (pq_percentile_batched), one date
-in ``solve()`` and every date of a backtest through ``percentile_batch``.
+in ``solve()`` and every date of a backtest through ``percentile_batch``.  RiskParity (beyond the
+reference: risk budgeting is not a QP) runs on the batched coordinate-descent kernel
+(pq_risk_parity_batched), one date in ``solve()`` and every date through ``risk_parity_batch``.
 """
 from __future__ import annotations
 
@@ -562,3 +564,136 @@ def percentile_results(index, w, bucket, counts) -> dict:
         members = np.flatnonzero(bucket == i)
         w_dict[i] = pd.Series(np.full(len(members), 1 / int(counts[i - 1])), index=index[members])
     return {"weights": dict(zip(index, w.tolist())), "w_dict": w_dict}
+
+
+RP_NAN_MESSAGE = "RiskParity: missing values in the return window are not supported"
+RP_REASONS = {1: "no convergence within max_sweeps sweeps",
+              2: "bad input (a zero-variance asset without a ridge, a one-row window, or non-finite data)"}
+
+
+class RiskParity(Optimization):
+    """Risk-parity / risk-budgeting portfolios (equal risk contribution by default): the weights
+    x > 0 with sum x = budget at which asset i carries the share b_i of the portfolio variance,
+    x_i (Sigma x)_i / x' Sigma x = b_i.  Not a QP: Spinu's convex form
+    y* = argmin_{y > 0} 1/2 y' Sigma y - sum_i b_i log y_i, x = budget y* / sum(y*), solved by
+    cyclical coordinate descent on the device (engine.risk_parity_weights, pq_risk_parity_batched)
+    on the window form Sigma = a Xc'Xc + c I of the ``covariance`` spec: 'pearson' (1/(T-1), 0),
+    'linear_shrinkage' c = lambda mean(diag S), 'ledoit_wolf' / 'oas' ((1-delta)/(T-1),
+    delta mean(diag S)) with the intensity of engine.shrinkage_intensity, 'duv' (0, 1).
+
+    ``risk_budget``: a dict or Series over the assets (None: equal budgets); an asset of the
+    date's selection without an entry is an error, entries must be > 0, and the budgets are
+    normalised to sum 1 over the selection.  ``params``: ``eps`` (1e-10, the relative residual
+    max_i |y_i (Sigma y)_i - b_i| / b_i at which a date is solved) and ``max_sweeps`` (500).
+
+    * Of the constraints only the budget's right-hand side is used, as the sum of the weights
+      (1 without a budget constraint).  Box and linear constraints are ignored -- the portfolio
+      is long-only by construction --, as PercentilePortfolios ignores the builders' constraints.
+    * ``check_positive_definite`` is moot: the window form is positive semi-definite.
+    * Missing values in the return window are not supported: ``solve()`` raises ValueError, a
+      backtest RuntimeError, with RP_NAN_MESSAGE.
+
+    ``solve()`` runs the kernel at batch 1 and fills ``results`` = {'weights', 'status',
+    'risk_contributions'}; ``status`` is False unless the date is PQ_RP_OK (the weights are then
+    None).  ``risk_parity_batch`` solves every date of a backtest chunk in one launch."""
+
+    def __init__(self, covariance: Optional[Covariance] = None, risk_budget=None, **kwargs):
+        super().__init__(**kwargs)
+        self.covariance = Covariance() if covariance is None else covariance
+        self.risk_budget = risk_budget
+        self.params.setdefault("eps", 1e-10)
+        self.params.setdefault("max_sweeps", 500)
+
+    def set_objective(self, optimization_data: OptimizationData) -> None:
+        self.objective = Objective(X=optimization_data["return_series"])
+
+    def budget_vector(self, universe) -> np.ndarray:
+        """The risk budgets over ``universe``, normalised to sum 1."""
+        universe = list(universe)
+        if self.risk_budget is None:
+            return np.full(len(universe), 1.0 / len(universe))
+        rb = self.risk_budget if isinstance(self.risk_budget, pd.Series) else pd.Series(dict(self.risk_budget))
+        missing = [a for a in universe if a not in rb.index]
+        if missing:
+            raise ValueError(f"RiskParity: risk_budget has no entry for {missing[:5]}"
+                             + (" ..." if len(missing) > 5 else ""))
+        b = rb.reindex(universe).to_numpy(dtype=np.float64)
+        if not np.all(np.isfinite(b)) or not np.all(b > 0):
+            raise ValueError("RiskParity: risk budgets must be finite and > 0")
+        return b / b.sum()
+
+    def budget_scale(self) -> float:
+        rhs = self.constraints.budget.get("rhs")
+        return 1.0 if rhs is None else float(rhs)
+
+    def window_form(self, panel, rows, tlen, dg):
+        """(a, c) per date of Sigma = a Xc'Xc + c I for the covariance spec (device tensors)."""
+        import torch
+        from . import engine
+        from .covariance import SHRINKAGE_METHODS, _shrink_lambda
+        method = self.covariance.spec["method"]
+        B, dev = int(rows.shape[0]), panel.device
+        if method == "duv":
+            return (torch.zeros(B, dtype=torch.float64, device=dev),
+                    torch.ones(B, dtype=torch.float64, device=dev))
+        a = 1.0 / (tlen.to(torch.float64) - 1.0)
+        md = dg[:, :panel.n].mean(dim=1) * a          # mean(diag S)
+        if method == "pearson":
+            return a, torch.zeros_like(a)
+        if method == "linear_shrinkage":
+            return a, _shrink_lambda(self.covariance.spec.get("lambda_covmat_regularization")) * md
+        if method in SHRINKAGE_METHODS:
+            delta, _ = engine.shrinkage_intensity(panel, rows, tlen, kind=method)
+            self.covariance.shrinkage_batch_ = delta
+            return (1.0 - delta) * a, delta * md
+        raise NotImplementedError("This method is not implemented yet")
+
+    def solve_windows(self, panel, rows, tlen, universe):
+        """Every window of the device row table in one launch -> (x, stats, status, form) on the
+        device; form = (mu, a, c), what risk_contributions needs."""
+        from . import engine
+        if panel.has_nan:
+            raise ValueError(RP_NAN_MESSAGE)
+        mu = panel.window_means(rows, tlen)
+        dg = panel.window_sumsq(rows, tlen, mu)
+        a, c = self.window_form(panel, rows, tlen, dg)
+        x, stats, status = engine.risk_parity_weights(
+            panel, rows, tlen, budgets=self.budget_vector(universe), a=a, c=c, scale=self.budget_scale(),
+            eps=float(self.params["eps"]), max_sweeps=int(self.params["max_sweeps"]), moments=(mu, dg))
+        return x, stats, status, (mu, a, c)
+
+    @staticmethod
+    def risk_contributions(panel, rows, tlen, form, x, i: int) -> np.ndarray:
+        """x_j (Sigma x)_j / x' Sigma x of date i from the window form (torch, on the device)."""
+        mu, a, c = form
+        T = int(tlen[i].item())
+        X = panel.R[rows[i, :T].long()] - mu[i, :panel.n]
+        xi = x[i]
+        m = xi * (a[i] * (X.T @ (X @ xi)) + c[i] * xi)
+        return (m / m.sum()).cpu().numpy()
+
+    def solve(self) -> bool:
+        from . import _lib, engine
+        X = self.objective["X"]
+        universe = list(X.columns) if isinstance(X, pd.DataFrame) else list(self.constraints.selection)
+        Xv = np.ascontiguousarray(to_numpy(X), dtype=np.float64)
+        if np.isnan(Xv).any():
+            raise ValueError(RP_NAN_MESSAGE)
+        T = Xv.shape[0]
+        panel = engine.Panel(Xv)
+        rows, tlen = panel.rows_to_device(np.arange(T, dtype=np.int32)[None], np.array([T], dtype=np.int32))
+        x, stats, status, form = self.solve_windows(panel, rows, tlen, universe)
+        ok = int(status[0].item()) == _lib.PQ_RP_OK
+        w = x[0].cpu().numpy().tolist() if ok else [None] * len(universe)
+        rc = self.risk_contributions(panel, rows, tlen, form, x, 0).tolist() if ok else [None] * len(universe)
+        self.results = {"weights": dict(zip(universe, w)), "status": ok,
+                        "risk_contributions": dict(zip(universe, rc))}
+        return ok
+
+    def risk_parity_batch(self, stage):
+        """Every date of a backtest chunk in one launch (the counterpart of
+        PercentilePortfolios.percentile_batch): (x, stats, status, form) on the device, the
+        assets being the constraints' selection (date-invariant builders)."""
+        if stage.batch == 0:
+            return None
+        return self.solve_windows(stage.panel, stage.rows, stage.tlen, self.constraints.selection)
