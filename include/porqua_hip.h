@@ -214,7 +214,9 @@ int pq_window_geomean(const double* panel, int64_t ldp, int32_t n, const int32_t
  * first window's sum of log(1 + x) directly, the later ones by the rows that enter / leave
  * (T + 2 (G - 1) logarithms per column and group instead of G T).  Replaces
  * pq_window_geomean for the daily mean-variance backtest (src/optimization.py:157-177,
- * per rebalance date of src/backtest.py:209-230).                                        */
+ * per rebalance date of src/backtest.py:209-230).  Entries with 1 + x <= 0 are counted,
+ * not summed: a window gives NaN if it holds one with 1 + x < 0, else -1 if it holds one
+ * with 1 + x == 0, as pq_window_geomean does, and later windows are unaffected.           */
 int pq_window_geomean_grouped(const double* panel, int64_t ldp, int32_t n, const int32_t* gdates,
                               int32_t ngroups, const int32_t* urows, int32_t umax,
                               const int32_t* uoff, const int32_t* tlen, double* mu,

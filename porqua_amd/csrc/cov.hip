@@ -119,6 +119,11 @@ __global__ __launch_bounds__(256) void k_window_moments_grp(const double* panel,
 // k_window_mean geo arithmetic: exp(sum log(1 + x) / T) - 1) in one sliding pass over the
 // group's union rows: the first window's log sum directly, each later one by the rows that
 // enter and leave -- T + 2 (G - 1) logarithms per column and group instead of G T.
+// A return of -100 % (1 + x == 0) or below (1 + x < 0; a NaN entry counts here too) has no
+// finite logarithm, and -inf or NaN would never leave a sliding sum again.  Such entries stay
+// out of the sum and are counted instead, the counts sliding with the rows: a window holding an
+// entry below -100 % gives NaN, one holding only -100 % entries gives -1, as the per-date kernel
+// does, and the windows after the row has left are exact again.
 __global__ __launch_bounds__(256) void k_window_geomean_grp(const double* panel, int64_t ldp, int n,
                                                             const int32_t* gdates, const int32_t* urows,
                                                             int umax, const int32_t* uoff,
@@ -136,6 +141,18 @@ __global__ __launch_bounds__(256) void k_window_geomean_grp(const double* panel,
   auto xv = [&](int u) { return panel[(int64_t)ur[u] * ldp + j]; };
   int lo = uoff[d0], hi = lo + T;
   double s = 0.0;
+  int nz = 0, nn = 0;   // window entries with 1 + x == 0 / with 1 + x < 0 (or NaN)
+  auto slide = [&](double v, bool enter) {
+    const double t = 1.0 + v;
+    if (t > 0.0) {
+      const double l = log(t);
+      if (enter) s += l; else s -= l;
+    } else if (t == 0.0) {
+      nz += enter ? 1 : -1;
+    } else {
+      nn += enter ? 1 : -1;
+    }
+  };
   {
     int u = lo;
     for (; u + 8 <= hi; u += 8) {
@@ -143,12 +160,12 @@ __global__ __launch_bounds__(256) void k_window_geomean_grp(const double* panel,
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = xv(u + e);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) s += log(1.0 + v[e]);
+      for (int e = 0; e < 8; ++e) slide(v[e], true);
     }
-    for (; u < hi; ++u) s += log(1.0 + xv(u));
+    for (; u < hi; ++u) slide(xv(u), true);
   }
   for (int b = d0;; ) {
-    mu[(int64_t)b * mu_stride + j] = exp(s / T) - 1.0;
+    mu[(int64_t)b * mu_stride + j] = nn ? __builtin_nan("") : nz ? -1.0 : exp(s / T) - 1.0;
     if (++b >= d1) break;
     const int nlo = uoff[b], nhi = nlo + T;
     for (int u = hi; u < nhi; u += 4) {   // entering
@@ -157,7 +174,7 @@ __global__ __launch_bounds__(256) void k_window_geomean_grp(const double* panel,
       for (int e = 0; e < 4; ++e) v[e] = xv(min(u + e, nhi - 1));
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        if (u + e < nhi) s += log(1.0 + v[e]);
+        if (u + e < nhi) slide(v[e], true);
     }
     for (int u = lo; u < nlo; u += 4) {   // leaving
       double v[4];
@@ -165,7 +182,7 @@ __global__ __launch_bounds__(256) void k_window_geomean_grp(const double* panel,
       for (int e = 0; e < 4; ++e) v[e] = xv(min(u + e, nlo - 1));
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        if (u + e < nlo) s -= log(1.0 + v[e]);
+        if (u + e < nlo) slide(v[e], false);
     }
     lo = nlo;
     hi = nhi;

@@ -1706,7 +1706,7 @@ class Panel:
         B, tmax = rows.shape
         mu = out if out is not None else torch.zeros((B, round_up(self.n, 64)), dtype=F64, device=self.device)
         fn = lib.pq_window_geomean if geometric else lib.pq_window_mean
-        _lib.check(fn(_ptr(self.R), self.n, self.n, _ptr(rows), _ptr(tlen), tmax, B, _ptr(mu),
+        _lib.check(fn(_ptr(self.R), self.R.stride(0), self.n, _ptr(rows), _ptr(tlen), tmax, B, _ptr(mu),
                       mu.stride(0), _stream()), "window means")
         return mu
 
@@ -1774,7 +1774,7 @@ class Panel:
         ld = round_up(self.n, 64)
         xty = torch.zeros((B, ld), dtype=F64, device=self.device)
         yty = torch.zeros(B, dtype=F64, device=self.device)
-        _lib.check(lib.pq_gram_xy_batched(_ptr(self.R), self.n, self.n, _ptr(self.bm), _ptr(rows),
+        _lib.check(lib.pq_gram_xy_batched(_ptr(self.R), self.R.stride(0), self.n, _ptr(self.bm), _ptr(rows),
                                           _ptr(tlen), tmax, B, _ptr(xty), xty.stride(0), _ptr(yty),
                                           _stream()), "pq_gram_xy_batched")
         return xty, yty
