@@ -548,7 +548,9 @@ int64_t pq_workspace_bytes(int32_t n, int32_t batch, int32_t mg, int32_t path, i
  * evals[b][0..ld) = diag of the diagonalised A (unsorted; 0 beyond n).  work:
  * pq_sym_eig_work_doubles(ld) doubles per matrix.  Sweeps of 64 x 64 subproblems (one
  * workgroup each, cyclic Jacobi in LDS) and MFMA tile updates, until a sweep rotates nothing
- * (at most max_sweeps; rotation threshold |a_pq| > tol sqrt|a_pp a_qq|).                  */
+ * (at most max_sweeps; an entry is rotated when |a_pq| > tol sqrt|a_pp a_qq| and
+ * |a_pq| > tol 2^-53 ||A||_F, the floor that lets exact null spaces converge; a rotation
+ * that rounds to the identity does not count as one).                                      */
 int64_t pq_sym_eig_work_doubles(int32_t ld);
 int pq_sym_eig_batched(double* A, int32_t ld, int64_t a_stride, int32_t n, int32_t batch, double* V,
                        int64_t v_stride, double* evals, int64_t e_stride, double* work, int64_t w_stride,

@@ -11,8 +11,8 @@
 // round every pair (I, J) of blocks is one 64 x 64 subproblem [A_II A_IJ; A_JI A_JJ]:
 //   k_jac_pairs   one workgroup per pair: the subproblem is diagonalised in LDS by cyclic
 //                 Jacobi (32 disjoint rotations per step, round-robin order, until no
-//                 off-diagonal entry exceeds tol sqrt|a_pp a_qq|), its 64 x 64 rotation W_P
-//                 is written out;
+//                 off-diagonal entry exceeds both tol sqrt|a_pp a_qq| and the absolute floor
+//                 tol 2^-53 ||A||_F of k_jac_scale), its 64 x 64 rotation W_P is written out;
 //   k_jac_apply   one workgroup per 64 x 64 tile of the pair grid: A[P, Q] <- W_P' A[P, Q] W_Q
 //                 (two MFMA tile products), and V[R, Q] <- V[R, Q] W_Q for the eigenvectors.
 // Sweeps repeat until a whole sweep rotates nothing (device flags: the launches of a
@@ -31,7 +31,7 @@ constexpr int JP = 65;          // LDS pitch of the subproblem / rotation
 struct JacCtx {
   double* A; int64_t a_stride;
   double* V; int64_t v_stride;  // NULL: eigenvalues only
-  double* work;                 // per matrix: npairs x 64 x 64 rotations + 2 x nrounds x npairs flags
+  double* work;                 // per matrix: npairs x 64 x 64 rotations + 2 x nrounds x npairs flags + ||A||_F
   int64_t w_stride;
   int ld, n, nbk, npairs, nrounds;
   double tol;
@@ -53,6 +53,10 @@ __device__ __forceinline__ double* jac_rot(const JacCtx& c, int b, int pair) {
 __device__ __forceinline__ double* jac_flags(const JacCtx& c, int b, int parity) {
   return c.work + (int64_t)b * c.w_stride + (int64_t)c.npairs * JS * JS +
          (int64_t)parity * c.nrounds * c.npairs;
+}
+// ||A_b||_F of the input (k_jac_scale): the one work double behind the flags
+__device__ __forceinline__ double* jac_scale(const JacCtx& c, int b) {
+  return c.work + (int64_t)b * c.w_stride + (int64_t)c.npairs * JS * JS + 2 * (int64_t)c.nrounds * c.npairs;
 }
 
 // did sweep `sweep - 1` rotate anything in matrix b?  (sweep 0: yes)
@@ -91,6 +95,9 @@ __global__ __launch_bounds__(256) void k_jac_pairs(JacCtx c, int sweep, int roun
   }
   if (threadIdx.x == 0) rot_flag = 0;
   __syncthreads();
+  // absolute floor of the rotation rule: inside a null space both diagonals are rounding
+  // noise and so is the relative threshold; entries below tol u ||A||_F move no eigenvalue
+  const double floor_abs = c.tol * 0x1p-53 * *jac_scale(c, b);
   int any_rot = 0;
   for (int isw = 0; isw < 30; ++isw) {
     int swept = 0;
@@ -102,12 +109,14 @@ __global__ __launch_bounds__(256) void k_jac_pairs(JacCtx c, int sweep, int roun
         rr_pair(k, step, JS, p, q);
         const double apq = S[p * JP + q], app = S[p * JP + p], aqq = S[q * JP + q];
         double cc = 1.0, ss = 0.0;
-        if (fabs(apq) > c.tol * sqrt(fabs(app) * fabs(aqq)) && fabs(apq) > 1e-300) {
+        if (fabs(apq) > c.tol * sqrt(fabs(app) * fabs(aqq)) && fabs(apq) > floor_abs && fabs(apq) > 1e-300) {
           const double tau = (aqq - app) / (2.0 * apq);
           const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
           cc = 1.0 / sqrt(1.0 + t * t);
           ss = t * cc;
-          rot_flag = 1;   // benign race: every writer stores 1
+          // tau * tau can overflow (t = 0): that rotation is the identity and must not count.
+          // benign race: every writer stores 1
+          if (ss != 0.0) rot_flag = 1;
         }
         cs[k] = cc; sn[k] = ss; pp[k] = p; qq[k] = q;
       }
@@ -240,6 +249,26 @@ __global__ __launch_bounds__(256) void k_jac_init(JacCtx c) {
   }
 }
 
+// ||A_b||_F of the leading n x n input (one workgroup per matrix; scaled by the largest
+// entry, so neither 1e-150 A nor 1e150 A leaves the range)
+__global__ __launch_bounds__(256) void k_jac_scale(JacCtx c) {
+  __shared__ double red[16];
+  const int b = blockIdx.x;
+  const double* A = c.A + (int64_t)b * c.a_stride;
+  const int total = c.n * c.n;
+  double m = 0.0;
+  for (int e = threadIdx.x; e < total; e += blockDim.x) m = fmax(m, fabs(A[(int64_t)(e / c.n) * c.ld + e % c.n]));
+  m = block_max(m, red);
+  double s = 0.0;
+  if (m > 0.0 && m < HUGE_VAL)
+    for (int e = threadIdx.x; e < total; e += blockDim.x) {
+      const double r = A[(int64_t)(e / c.n) * c.ld + e % c.n] / m;
+      s += r * r;
+    }
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) *jac_scale(c, b) = (m > 0.0 && m < HUGE_VAL) ? m * sqrt(s) : m;
+}
+
 __global__ __launch_bounds__(256) void k_jac_diag(JacCtx c, double* evals, int64_t e_stride) {
   const int b = blockIdx.y;
   const double* A = c.A + (int64_t)b * c.a_stride;
@@ -277,9 +306,10 @@ __global__ __launch_bounds__(256) void k_psd_form(const double* V, int64_t v_str
     for (int e = threadIdx.x; e < TB * TB; e += blockDim.x) {
       const int i = e >> 6, k = e & 63;
       const int kk = k0 + k;
-      const double sc = kk < n ? sqrt(fmax(lam[kk], 0.0)) : 0.0;
-      SA[k * LDW + i] = Vb[(int64_t)(I * TB + i) * ld + kk] * sc;
-      SB[k * LDW + i] = Vb[(int64_t)(J * TB + i) * ld + kk] * sc;
+      const bool live = kk < n;                                    // padding columns are skipped,
+      const double sc = live ? sqrt(fmax(lam[kk], 0.0)) : 0.0;     // not multiplied by 0 (NaN there)
+      SA[k * LDW + i] = live ? Vb[(int64_t)(I * TB + i) * ld + kk] * sc : 0.0;
+      SB[k * LDW + i] = live ? Vb[(int64_t)(J * TB + i) * ld + kk] * sc : 0.0;
     }
     __syncthreads();
     mma_lds(acc, SA, SB, TB);
@@ -306,7 +336,7 @@ __global__ __launch_bounds__(256) void k_tile_gemm(const double* A, int64_t sa, 
 
 extern "C" int64_t pq_sym_eig_work_doubles(int32_t ld) {
   const int nbk = ld / pq::JB, np = nbk / 2, nr = nbk - 1;
-  return (int64_t)np * pq::JS * pq::JS + 2 * (int64_t)nr * np;
+  return (int64_t)np * pq::JS * pq::JS + 2 * (int64_t)nr * np + 1;
 }
 
 extern "C" int pq_sym_eig_batched(double* A, int32_t ld, int64_t a_stride, int32_t n, int32_t batch, double* V,
@@ -328,6 +358,7 @@ extern "C" int pq_sym_eig_batched(double* A, int32_t ld, int64_t a_stride, int32
   c.tol = tol;
   const dim3 blk(256);
   hipLaunchKernelGGL(pq::k_jac_init, dim3(64, batch), blk, 0, str, c);
+  hipLaunchKernelGGL(pq::k_jac_scale, dim3(batch), blk, 0, str, c);
   const int ntile = c.npairs * c.npairs + (V ? (ld / 64) * c.npairs : 0);
   for (int s = 0; s < max_sweeps; ++s)
     for (int r = 0; r < c.nrounds; ++r) {

@@ -637,7 +637,9 @@ class EigCap:
     block-Jacobi solver (jacobi.hip, helper_functions.sym_eig, 'jacobi'), once per date.
     Measured for the 64 window Grams of config 5 (profiles/r03k_exp_eigh.log): syevd 10.4 ms,
     the block-Jacobi kernels 64.5 ms (eigenvalues to 1.2e-12) -- the Jacobi form serves the
-    nearestPD repair, whose matrices need no ordering and few sweeps.
+    nearestPD repair, whose matrices need no ordering.  (Not few sweeps: a rank-deficient
+    covariance takes more than a dense matrix of its size, 24 of the 30 allowed at n = 1000,
+    T = 252)
 
     rows / tlen / mu: per-date device tensors (every tlen == tmax); pdate: date of each
     problem (int32, device); Cg: the shared general rows (qb.Cg, mg <= 4)."""

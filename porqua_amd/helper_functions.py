@@ -156,8 +156,11 @@ def _tile_gemm(A, ta, B, tb):
 
 
 def _spacing(x: torch.Tensor) -> torch.Tensor:
-    """np.spacing for positive finite FP64 values, on the device."""
+    """np.spacing for non-negative finite FP64 values, on the device: 2^(e - 53) for
+    x = m 2^e, 0.5 <= m < 1, and the smallest subnormal 2^-1074 for 0, the subnormals and the
+    normals below 2^-1021 (whose frexp exponent would undershoot it)."""
     _, e = torch.frexp(x)
+    e = torch.where(x == 0, torch.full_like(e, -1021), e).clamp(min=-1021)
     return torch.ldexp(torch.ones_like(x), (e - 53).to(torch.int32))
 
 
