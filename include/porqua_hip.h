@@ -653,6 +653,38 @@ int pq_risk_parity_batched(const pq_lowrank* lr, int32_t n, int32_t batch, const
                            const double* budget, int64_t ldb, double scale, double eps, int32_t max_sweeps,
                            double* x, int64_t ldx, double* stats, int32_t* status, void* stream);
 
+/* Hierarchical risk parity (Lopez de Prado 2016) of a batch of dates on the dense
+ * Sigma_b = alpha[b] S_b + c[b] I; S is batch x ld x ld, row-major and symmetric, ld >= n, and
+ * only its first n columns and rows are read (each row once by the tree, the cross blocks of the
+ * bisection twice more: about 2 x 8 n^2 bytes per date).  Per date:
+ *   rho_ij = Sigma_ij / sqrt(Sigma_ii Sigma_jj) clipped to [-1, 1], D_ij = sqrt((1 - rho_ij) / 2);
+ *   the single-linkage tree of D exactly as scipy.cluster.hierarchy.linkage(.., 'single') builds
+ *   it: Prim's minimum spanning tree from asset 0 (best[j] updated on strict <, the lowest index
+ *   among the minima joins next), the n - 1 edges stably sorted by distance, merge k creating
+ *   cluster n + k from the current roots of the edge's ends, the smaller id first (the order is
+ *   taken on 1 - rho, of which D is a monotone function);
+ *   order[b] = the leaves in pre-order, first child before second (scipy's leaves_list);
+ *   recursive bisection: from w = 1, every list of L > 1 ordered assets is split into its first
+ *   L / 2 and its remaining entries, w[left] *= a, w[right] *= 1 - a with a = 1 - v_l / (v_l + v_r),
+ *   v_c = u' Sigma_cc u, u = (1 / diag Sigma_c) / sum(1 / diag Sigma_c);   x[b] = scale w, not
+ *   renormalised (its sum is scale up to rounding).
+ * link (optional, NULL: skipped): batch x (n - 1) x 4 doubles, scipy's Z: child, child, distance,
+ * size.  stats[b] = { x' Sigma x, the smallest gap between consecutive sorted merge distances
+ * (+inf for n <= 2: the diagnostic of a numerically ambiguous tree) }.  status[b]: PQ_HRP_OK, or
+ * PQ_HRP_BAD_INPUT -- some Sigma_ii non-finite or <= 0, a non-finite off-diagonal entry among the
+ * first n columns and rows, alpha or c negative or non-finite --, for which x[b], stats[b] and
+ * link[b] are NaN and order[b] is -1.  n = 1: x = scale, order = {0}, no merges.  One 256-thread
+ * workgroup per date, the tree and the weights in LDS: a date never affects another date, and
+ * without floating-point atomics the same input gives the same bits.
+ * 1 <= n <= PQ_HRP_NMAX, ld, ldx, ldo >= n; x is batch x ldx, order batch x ldo (int32), stats
+ * batch x 2.  The call does not synchronise; only host-checkable arguments return an error.   */
+#define PQ_HRP_OK 0
+#define PQ_HRP_BAD_INPUT 1
+#define PQ_HRP_NMAX 1024
+int pq_hrp_batched(const double* S, int64_t ld, int32_t n, int32_t batch, const double* alpha, const double* c,
+                   double scale, double* x, int64_t ldx, int32_t* order, int64_t ldo, double* link, double* stats,
+                   int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

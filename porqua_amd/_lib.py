@@ -34,6 +34,10 @@ PQ_PCT_MAX_BUCKETS = 256
 PQ_RP_OK, PQ_RP_MAX_SWEEPS, PQ_RP_BAD_INPUT = range(3)
 PQ_RP_TMAX = 1024
 
+# pq_hrp_batched: per-date status and the most assets of a date (include/porqua_hip.h)
+PQ_HRP_OK, PQ_HRP_BAD_INPUT = range(2)
+PQ_HRP_NMAX = 1024
+
 PQ_PG_RECORD = 384                   # doubles per problem of the grouped polish record
 PQ_PG_PASS_SCRATCH = 123537          # doubles per slide group of the split polish window passes
 PQ_PG_PENDING, PQ_PG_DONE, PQ_PG_FALLBACK, PQ_PG_SKIP = range(4)
@@ -235,6 +239,8 @@ _EXPORTS = {
     "pq_risk_parity_batched": ([ctypes.POINTER(PQLowRank), c_int32, c_int32, c_dp, c_dp, c_dp, c_int64,
                                 ctypes.c_double, ctypes.c_double, c_int32, c_dp, c_int64, c_dp, c_dp, c_dp],
                                c_int32),
+    "pq_hrp_batched": ([c_dp, c_int64, c_int32, c_int32, c_dp, c_dp, ctypes.c_double, c_dp, c_int64, c_dp, c_int64,
+                        c_dp, c_dp, c_dp, c_dp], c_int32),
 }
 
 _lib = None

@@ -21,7 +21,7 @@ loop runs in two phases instead of one serial QP per date:
 PercentilePortfolios (no QP) batches the same way: phase A, then the scores of every date
 from the device geometric means and one ranking launch (``_run_percentile``).  RiskParity (no QP
 either) likewise: phase A, then every date's coordinate descent in one launch
-(``_run_risk_parity``).
+(``_run_risk_parity``), HierarchicalRiskParity likewise (``_run_hrp``).
 
 Dates are independent in the reference; an ``append_fun`` that mutates
 state read by later dates is not supported in batched mode (set settings['batched'] = False
@@ -354,6 +354,10 @@ class Backtest:
         elif hasattr(bs.optimization, "risk_parity_batch") and _batchable(bs):
             # risk parity: not a QP either; every date in one coordinate-descent launch
             if self._run_risk_parity(bs):
+                return None
+        elif hasattr(bs.optimization, "hrp_batch") and _batchable(bs):
+            # hierarchical risk parity: a tree and closed-form splits per date, one workgroup each
+            if self._run_hrp(bs):
                 return None
         elif bs.optimization.params.get("solver_name") in ENGINE_SOLVERS and _batchable(bs):
             if self._run_batched(bs):
@@ -774,6 +778,64 @@ class Backtest:
             rc = opt.risk_contributions(panel, stage.rows, stage.tlen, form, x, i)
             return {"weights": dict(zip(keys, W[i].tolist())), "status": True,
                     "risk_contributions": dict(zip(keys, rc.tolist()))}
+        if bs.settings.get("append_fun") is None:
+            self.strategy.portfolios.extend(Portfolio._from_row(d, keys, W[i]) for i, d in enumerate(rebdates))
+        else:
+            for i, d in enumerate(rebdates):
+                opt.results = results(i)
+                self._after_solve(bs, d)
+        # the optimisation's results hold the last date's, as after the serial loop
+        opt.results = results(len(rebdates) - 1)
+        return True
+
+    def _run_hrp(self, bs) -> bool:
+        """Batched run of HierarchicalRiskParity: phase A as for the QP path (static selection,
+        panel upload, window rows), every date's tree and weights on the device (``hrp_batch``),
+        one copy of weights, stats and status to the host, and phase C.  A date that is not
+        PQ_HRP_OK raises RuntimeError naming the date; a panel with missing values raises
+        RuntimeError(HRP_NAN_MESSAGE), as the serial loop does.  False: the serial loop has to run
+        (no return-series width).
+
+        Under an initialised process group every rank computes all dates and no collective
+        runs, as for RiskParity."""
+        import torch
+        from . import _lib, engine
+        from .optimization import HRP_NAN_MESSAGE, HRP_REASON
+        rebdates = list(bs.settings["rebdates"])
+        if not rebdates:
+            return False
+        opt = bs.optimization
+        bs.prepare_rebalancing(rebalancing_date=rebdates[0])
+        universe = bs.selection.selected
+        ws = _stage_windows(bs, universe, rebdates)
+        if ws is None:
+            return False
+        _, upload, _, rows, tlen = ws
+        dev = engine.default_device()
+        panel = engine.Panel(upload.result(), None, device=dev)
+        if panel.has_nan:
+            raise RuntimeError(HRP_NAN_MESSAGE)
+        out = opt.hrp_batch(BatchStage(panel, rows, tlen, dev))
+        if out is None:
+            return False
+        x, order, stats, status, Z = out
+        n = len(universe)
+        Ht, H = _pinned_panel(len(rebdates), n + 3)
+        Ht.copy_(torch.cat([x, stats, status.to(torch.float64)[:, None]], 1))
+        W, stats_h, status_h = H[:, :n], H[:, n:n + 2], H[:, n + 2].astype(np.int32)
+        bad = np.flatnonzero(status_h != _lib.PQ_HRP_OK)
+        if bad.size:
+            raise RuntimeError(f"HierarchicalRiskParity: rebalancing date {rebdates[bad[0]]}: {HRP_REASON}")
+        order_h = order.cpu().numpy()
+        self.stats = {"dates": len(rebdates), "solved": len(rebdates), "status": status_h, "path": "hrp",
+                      "variance": stats_h[:, 0], "min_gap": stats_h[:, 1], "order": order_h}
+        if not bs.settings.get("quiet"):
+            print(f"Solved {len(rebdates)} hierarchical-risk-parity dates on the device")
+        keys = list(universe)
+
+        def results(i):
+            return {"weights": dict(zip(keys, W[i].tolist())), "status": True,
+                    "order": [keys[j] for j in order_h[i].tolist()], "linkage": Z[i].cpu().numpy()}
         if bs.settings.get("append_fun") is None:
             self.strategy.portfolios.extend(Portfolio._from_row(d, keys, W[i]) for i, d in enumerate(rebdates))
         else:

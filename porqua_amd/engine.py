@@ -1930,7 +1930,7 @@ def percentile_weights(scores: torch.Tensor, n_percentiles: int, sign: float = -
     return w, bucket, counts, th, status
 
 
-def _per_date(v, B: int, dev, what: str):
+def _per_date(v, B: int, dev, what: str, who: str = "risk_parity_weights"):
     """A per-date FP64 device vector from a scalar or a (B,) tensor / array."""
     if isinstance(v, torch.Tensor):
         v = v.to(dev, dtype=F64).flatten()
@@ -1939,7 +1939,7 @@ def _per_date(v, B: int, dev, what: str):
     if v.numel() == 1:
         v = v.expand(B)
     if v.numel() != B:
-        raise ValueError(f"risk_parity_weights: {what} must be a scalar or one value per date")
+        raise ValueError(f"{who}: {what} must be a scalar or one value per date")
     return v.contiguous()
 
 
@@ -1992,3 +1992,52 @@ def risk_parity_weights(panel: "Panel", rows, tlen, budgets=None, a=None, c=None
                                           float(eps), int(max_sweeps), _ptr(x), x.stride(0), _ptr(stats),
                                           _ptr(status), _stream()), "pq_risk_parity_batched")
     return x, stats, status
+
+
+HRP_CHUNK_BYTES = 2 << 30   # the dense covariance buffer of hrp_weights stays below this
+
+
+def hrp_weights(panel: "Panel", rows, tlen, alpha=None, c=None, centred: bool = True, scale: float = 1.0,
+                linkage: bool = False, chunk_bytes: int = HRP_CHUNK_BYTES, plan: "SlidePlan | None" = None):
+    """Hierarchical-risk-parity weights of every window (pq_hrp_batched): per date the
+    single-linkage tree of the correlation distance of Sigma = alpha S + c I (SciPy's conventions),
+    its leaves in pre-order and the recursive bisection of that order by inverse-variance cluster
+    variances; nothing is inverted or factored.  S is the window's sample covariance (Panel.cov
+    mode 0, ddof = 1; ``centred`` False: the Gram X'X, mode 1), formed per chunk of dates so that
+    the dense buffer stays under ``chunk_bytes``; one kernel launch per chunk.  ``alpha`` / ``c``:
+    scalars or one value per date, defaults 1 and 0.  ``plan``: a SlidePlan of the row table where
+    the caller has one (it covers the whole batch, so the batch has to fit one chunk).  At most
+    _lib.PQ_HRP_NMAX assets.  Returns (x [B, n], order [B, n] int32, stats [B, 2] = x' Sigma x and
+    the smallest gap between consecutive merge distances, status [B] int32: _lib.PQ_HRP_*), and
+    with ``linkage`` also Z [B, n - 1, 4] in SciPy's layout, all on the device; a date whose
+    status is PQ_HRP_BAD_INPUT (a one-row window, a zero-variance asset without a ridge,
+    non-finite data) has NaN weights and order -1.  Does not synchronise."""
+    lib = _lib.load()
+    B, n, dev = int(rows.shape[0]), panel.n, panel.device
+    if not 1 <= n <= _lib.PQ_HRP_NMAX:
+        raise ValueError(f"hrp_weights: n = {n} outside 1..{_lib.PQ_HRP_NMAX} (the tree of one date lives in LDS)")
+    x = torch.empty((B, n), dtype=F64, device=dev)
+    order = torch.empty((B, n), dtype=torch.int32, device=dev)
+    stats = torch.empty((B, 2), dtype=F64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    Z = torch.empty((B, n - 1, 4), dtype=F64, device=dev) if linkage else None
+    out = (x, order, stats, status) + ((Z,) if linkage else ())
+    if B == 0:
+        return out
+    rows = rows.contiguous()
+    alpha = _per_date(1.0 if alpha is None else alpha, B, dev, "alpha", "hrp_weights")
+    c = _per_date(0.0 if c is None else c, B, dev, "c", "hrp_weights")
+    ld = round_up(n, 64)
+    per = max(1, min(B, int(chunk_bytes) // (8 * ld * ld)))
+    if plan is not None and per < B:
+        raise ValueError("hrp_weights: a SlidePlan covers the whole batch; it needs chunk_bytes >= "
+                         f"{8 * ld * ld * B} here")
+    buf = torch.empty((per, ld, ld), dtype=F64, device=dev)
+    for b0 in range(0, B, per):
+        b1 = min(B, b0 + per)
+        S = panel.cov(rows[b0:b1], tlen[b0:b1], mode=0 if centred else 1, out=buf[:b1 - b0], plan=plan)
+        _lib.check(lib.pq_hrp_batched(_ptr(S), ld, n, b1 - b0, _ptr(alpha[b0:]), _ptr(c[b0:]), float(scale),
+                                      _ptr(x[b0:]), x.stride(0), _ptr(order[b0:]), order.stride(0),
+                                      _ptr(Z[b0:]) if linkage and n > 1 else None, _ptr(stats[b0:]),
+                                      _ptr(status[b0:]), _stream()), "pq_hrp_batched")
+    return out

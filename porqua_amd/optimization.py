@@ -21,7 +21,9 @@ LAD runs on the batched device IPM of porqua_amd/lad.py; PercentilePortfolios (r
 the QP path) runs on the batched order-statistics kernel (pq_percentile_batched), one date
 in ``solve()`` and every date of a backtest through ``percentile_batch``.  RiskParity (beyond the
 reference: risk budgeting is not a QP) runs on the batched coordinate-descent kernel
-(pq_risk_parity_batched), one date in ``solve()`` and every date through ``risk_parity_batch``.
+(pq_risk_parity_batched), one date in ``solve()`` and every date through ``risk_parity_batch``;
+HierarchicalRiskParity on the batched tree-and-bisection kernel (pq_hrp_batched), through
+``hrp_batch``.
 """
 from __future__ import annotations
 
@@ -566,6 +568,33 @@ def percentile_results(index, w, bucket, counts) -> dict:
     return {"weights": dict(zip(index, w.tolist())), "w_dict": w_dict}
 
 
+def covariance_window_form(covariance, panel, rows, tlen, dg):
+    """(a, c) per date (device tensors) of the window form Sigma = a Xc'Xc + c I of a Covariance
+    spec -- 'pearson' (1/(T-1), 0), 'linear_shrinkage' c = lambda mean(diag S), 'ledoit_wolf' /
+    'oas' ((1-delta)/(T-1), delta mean(diag S)) with the intensity of engine.shrinkage_intensity
+    (left in ``covariance.shrinkage_batch_``), 'duv' (0, 1) --, shared by RiskParity and
+    HierarchicalRiskParity.  ``dg``: diag(Xc'Xc) of every window (Panel.window_sumsq)."""
+    import torch
+    from . import engine
+    from .covariance import SHRINKAGE_METHODS, _shrink_lambda
+    method = covariance.spec["method"]
+    B, dev = int(rows.shape[0]), panel.device
+    if method == "duv":
+        return (torch.zeros(B, dtype=torch.float64, device=dev),
+                torch.ones(B, dtype=torch.float64, device=dev))
+    a = 1.0 / (tlen.to(torch.float64) - 1.0)
+    md = dg[:, :panel.n].mean(dim=1) * a          # mean(diag S)
+    if method == "pearson":
+        return a, torch.zeros_like(a)
+    if method == "linear_shrinkage":
+        return a, _shrink_lambda(covariance.spec.get("lambda_covmat_regularization")) * md
+    if method in SHRINKAGE_METHODS:
+        delta, _ = engine.shrinkage_intensity(panel, rows, tlen, kind=method)
+        covariance.shrinkage_batch_ = delta
+        return (1.0 - delta) * a, delta * md
+    raise NotImplementedError("This method is not implemented yet")
+
+
 RP_NAN_MESSAGE = "RiskParity: missing values in the return window are not supported"
 RP_REASONS = {1: "no convergence within max_sweeps sweeps",
               2: "bad input (a zero-variance asset without a ridge, a one-row window, or non-finite data)"}
@@ -628,25 +657,7 @@ class RiskParity(Optimization):
 
     def window_form(self, panel, rows, tlen, dg):
         """(a, c) per date of Sigma = a Xc'Xc + c I for the covariance spec (device tensors)."""
-        import torch
-        from . import engine
-        from .covariance import SHRINKAGE_METHODS, _shrink_lambda
-        method = self.covariance.spec["method"]
-        B, dev = int(rows.shape[0]), panel.device
-        if method == "duv":
-            return (torch.zeros(B, dtype=torch.float64, device=dev),
-                    torch.ones(B, dtype=torch.float64, device=dev))
-        a = 1.0 / (tlen.to(torch.float64) - 1.0)
-        md = dg[:, :panel.n].mean(dim=1) * a          # mean(diag S)
-        if method == "pearson":
-            return a, torch.zeros_like(a)
-        if method == "linear_shrinkage":
-            return a, _shrink_lambda(self.covariance.spec.get("lambda_covmat_regularization")) * md
-        if method in SHRINKAGE_METHODS:
-            delta, _ = engine.shrinkage_intensity(panel, rows, tlen, kind=method)
-            self.covariance.shrinkage_batch_ = delta
-            return (1.0 - delta) * a, delta * md
-        raise NotImplementedError("This method is not implemented yet")
+        return covariance_window_form(self.covariance, panel, rows, tlen, dg)
 
     def solve_windows(self, panel, rows, tlen, universe):
         """Every window of the device row table in one launch -> (x, stats, status, form) on the
@@ -697,3 +708,82 @@ class RiskParity(Optimization):
         if stage.batch == 0:
             return None
         return self.solve_windows(stage.panel, stage.rows, stage.tlen, self.constraints.selection)
+
+
+HRP_NAN_MESSAGE = "HierarchicalRiskParity: missing values in the return window are not supported"
+HRP_REASON = "bad input (a zero-variance asset without a ridge, a one-row window, or non-finite data)"
+
+
+class HierarchicalRiskParity(Optimization):
+    """Hierarchical risk parity (Lopez de Prado 2016): the single-linkage tree of the correlation
+    distance sqrt((1 - rho) / 2) with SciPy's conventions, the assets in its leaf order, and the
+    recursive bisection of that order, each half weighted by the other's inverse-variance cluster
+    variance.  Not a QP and nothing is inverted or factored, so it is defined where the sample
+    covariance is singular (more assets than window rows).  Every date is one workgroup of
+    pq_hrp_batched (engine.hrp_weights) on the dense Sigma of the ``covariance`` spec: 'pearson',
+    'linear_shrinkage', 'ledoit_wolf' / 'oas' (the intensity of engine.shrinkage_intensity), 'duv'
+    -- the (a, c) mapping of RiskParity (covariance_window_form), as Sigma = alpha S + c I on the
+    sample covariance S.  ``linkage``: 'single' only.  At most _lib.PQ_HRP_NMAX assets.
+
+    * Of the constraints only the budget's right-hand side is used, as the sum of the weights
+      (1 without a budget constraint).  Box and linear constraints are ignored -- the portfolio
+      is long-only by construction --, as RiskParity ignores them.
+    * Missing values in the return window are not supported: ``solve()`` raises ValueError, a
+      backtest RuntimeError, with HRP_NAN_MESSAGE.
+
+    ``solve()`` runs the kernel at batch 1 and fills ``results`` = {'weights', 'status', 'order'
+    (the asset names in leaf order), 'linkage' (SciPy's Z as a numpy array)}; ``status`` is False
+    unless the date is PQ_HRP_OK (the weights are then None).  ``hrp_batch`` solves every date of
+    a backtest chunk."""
+
+    def __init__(self, covariance: Optional[Covariance] = None, linkage: str = "single", **kwargs):
+        super().__init__(**kwargs)
+        if linkage != "single":
+            raise NotImplementedError(f"HierarchicalRiskParity: linkage '{linkage}' is not implemented (only 'single')")
+        self.covariance = Covariance() if covariance is None else covariance
+        self.linkage = linkage
+
+    def set_objective(self, optimization_data: OptimizationData) -> None:
+        self.objective = Objective(X=optimization_data["return_series"])
+
+    def budget_scale(self) -> float:
+        rhs = self.constraints.budget.get("rhs")
+        return 1.0 if rhs is None else float(rhs)
+
+    def solve_windows(self, panel, rows, tlen, linkage: bool = False):
+        """Every window of the device row table -> engine.hrp_weights' tuple, on the device."""
+        from . import engine
+        if panel.has_nan:
+            raise ValueError(HRP_NAN_MESSAGE)
+        mu = panel.window_means(rows, tlen)
+        dg = panel.window_sumsq(rows, tlen, mu)
+        a, c = covariance_window_form(self.covariance, panel, rows, tlen, dg)
+        # Sigma = a Xc'Xc + c I = alpha S + c I on the sample covariance S = Xc'Xc / (T - 1)
+        alpha = a * (tlen.to(a.dtype) - 1.0)
+        return engine.hrp_weights(panel, rows, tlen, alpha=alpha, c=c, scale=self.budget_scale(), linkage=linkage)
+
+    def solve(self) -> bool:
+        from . import _lib, engine
+        X = self.objective["X"]
+        universe = list(X.columns) if isinstance(X, pd.DataFrame) else list(self.constraints.selection)
+        Xv = np.ascontiguousarray(to_numpy(X), dtype=np.float64)
+        if np.isnan(Xv).any():
+            raise ValueError(HRP_NAN_MESSAGE)
+        T = Xv.shape[0]
+        panel = engine.Panel(Xv)
+        rows, tlen = panel.rows_to_device(np.arange(T, dtype=np.int32)[None], np.array([T], dtype=np.int32))
+        x, order, stats, status, Z = self.solve_windows(panel, rows, tlen, linkage=True)
+        ok = int(status[0].item()) == _lib.PQ_HRP_OK
+        w = x[0].cpu().numpy().tolist() if ok else [None] * len(universe)
+        leaf = [universe[i] for i in order[0].cpu().numpy().tolist()] if ok else None
+        self.results = {"weights": dict(zip(universe, w)), "status": ok, "order": leaf,
+                        "linkage": Z[0].cpu().numpy() if ok else None}
+        return ok
+
+    def hrp_batch(self, stage):
+        """Every date of a backtest chunk (the counterpart of RiskParity.risk_parity_batch):
+        (x, order, stats, status, Z) on the device, the assets being the constraints' selection
+        (date-invariant builders)."""
+        if stage.batch == 0:
+            return None
+        return self.solve_windows(stage.panel, stage.rows, stage.tlen, linkage=True)
