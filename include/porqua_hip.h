@@ -685,6 +685,40 @@ int pq_hrp_batched(const double* S, int64_t ld, int32_t n, int32_t batch, const 
                    double scale, double* x, int64_t ldx, int32_t* order, int64_t ldo, double* link, double* stats,
                    int32_t* status, void* stream);
 
+/* pq_hrp_batched with the linkage of the tree chosen by ``method``.  PQ_HRP_SINGLE is
+ * pq_hrp_batched itself, bit for bit, and work may be NULL.  For the four others the tree is the
+ * one scipy.cluster.hierarchy.linkage(squareform(D), method) builds, in all four columns of link:
+ *   D_ij = sqrt(key_ij / 2) with the key 1 - clip((alpha S_ij)(isd_i isd_j)) of the single-linkage
+ *   stage, taken from the upper triangle of S and mirrored, as a full symmetric n x n matrix in
+ *   the date's slab of work;
+ *   the nearest-neighbour chain: an empty chain starts at the lowest live index; from the chain's
+ *   top x the previous element y is the candidate, and a live i != x replaces it only where
+ *   D_xi is strictly smaller (i upward: the lowest index among the minima); the previous element
+ *   merges with x, anything else is pushed.  A merge records (min, max, D_xy) of the two slots,
+ *   retires the lower one and stores in the upper one the Lance-Williams update against every
+ *   live i, in SciPy's operation order without contraction, division and root correctly rounded:
+ *     complete  max(d_xi, d_yi)                         weighted  (d_xi + d_yi) / 2
+ *     average   (n_x d_xi + n_y d_yi) / (n_x + n_y)
+ *     ward      sqrt(((n_i + n_x) d_xi^2 + (n_i + n_y) d_yi^2 - n_i d_xy^2) / (n_x + n_y + n_i));
+ *   the merges stably sorted by distance and labelled by a union-find (the smaller root first,
+ *   the sizes the union-find's).
+ * The leaf order, the bisection, link, stats and status are pq_hrp_batched's; stats[b][1] is the
+ * smallest gap between consecutive sorted merge distances of this tree.  A date whose chain does
+ * not end within 4 n scans (it needs at most 3 n) is PQ_HRP_BAD_INPUT.
+ * work: batch x n x ldw doubles, ldw >= n, scratch (contents unspecified after the call; only
+ * the first n columns of a row are written); about 8 n^2 bytes more traffic per date for the
+ * fill, 8 n per scan and 24 n more per merge.  method outside [0, 4], work NULL for a method that needs
+ * it and ldw < n are errors, as are pq_hrp_batched's; on an error nothing is launched.          */
+#define PQ_HRP_SINGLE 0
+#define PQ_HRP_COMPLETE 1
+#define PQ_HRP_AVERAGE 2
+#define PQ_HRP_WEIGHTED 3
+#define PQ_HRP_WARD 4
+int pq_hrp_linkage_batched(const double* S, int64_t ld, int32_t n, int32_t batch, const double* alpha,
+                           const double* c, double scale, int32_t method, double* work, int64_t ldw, double* x,
+                           int64_t ldx, int32_t* order, int64_t ldo, double* link, double* stats, int32_t* status,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,10 @@ PQ_RP_TMAX = 1024
 # pq_hrp_batched: per-date status and the most assets of a date (include/porqua_hip.h)
 PQ_HRP_OK, PQ_HRP_BAD_INPUT = range(2)
 PQ_HRP_NMAX = 1024
+# pq_hrp_linkage_batched: the method of the tree
+PQ_HRP_SINGLE, PQ_HRP_COMPLETE, PQ_HRP_AVERAGE, PQ_HRP_WEIGHTED, PQ_HRP_WARD = range(5)
+HRP_METHODS = {"single": PQ_HRP_SINGLE, "complete": PQ_HRP_COMPLETE, "average": PQ_HRP_AVERAGE,
+               "weighted": PQ_HRP_WEIGHTED, "ward": PQ_HRP_WARD}
 
 PQ_PG_RECORD = 384                   # doubles per problem of the grouped polish record
 PQ_PG_PASS_SCRATCH = 123537          # doubles per slide group of the split polish window passes
@@ -241,6 +245,8 @@ _EXPORTS = {
                                c_int32),
     "pq_hrp_batched": ([c_dp, c_int64, c_int32, c_int32, c_dp, c_dp, ctypes.c_double, c_dp, c_int64, c_dp, c_int64,
                         c_dp, c_dp, c_dp, c_dp], c_int32),
+    "pq_hrp_linkage_batched": ([c_dp, c_int64, c_int32, c_int32, c_dp, c_dp, ctypes.c_double, c_int32, c_dp, c_int64,
+                                c_dp, c_int64, c_dp, c_int64, c_dp, c_dp, c_dp, c_dp], c_int32),
 }
 
 _lib = None

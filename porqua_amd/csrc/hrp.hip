@@ -25,9 +25,31 @@
 //              entry of S once: n^2 / 2 entries over all levels.  A second pass over the same
 //              blocks with the final weights gives x' Sigma x.
 //
+// The complete, average, weighted and Ward trees (k_hrp_link) replace Prim and the run merges by
+// SciPy's nearest-neighbour chain on a distance matrix in a global work slab of the date:
+//
+//   D          D_ij = sqrt(key_ij / 2) with Prim's key, from the upper triangle of S and mirrored
+//              (SciPy's condensed form), four rows of S in flight; every entry of S is checked here,
+//              so the chain only ever sees finite numbers
+//   chain      thread t owns the columns 4t .. 4t+3 and their cluster sizes (registers; 0: dead).
+//              A scan reads row x of the chain's top -- contiguous --, takes Prim's argmin over
+//              the live columns but x, and the owners of x and of the previous element y publish
+//              their sizes and D_xy with it: one barrier.  Only a strictly smaller minimum
+//              replaces y; otherwise x and y merge: rows x and y are read contiguously, the
+//              Lance-Williams update in SciPy's operation order (no contraction, correctly rounded
+//              division and root) is written to row y contiguously and to column y strided, and a
+//              second barrier publishes it together with the lowest live column, where an empty
+//              chain restarts.  At most 3n scans; the loop is capped at 4n (the failure path).
+//   sort       as above, on (distance, merge index)
+//   merges     a union-find with path compression over the recorded slots (lane 0), the smaller
+//              root first; the sizes are the union-find's, as in SciPy's label(), not the chain's
+//
 // LDS: 38 bytes per asset slot (pow2ceil(n) slots), the tree's arrays aliased by the bisection's:
-// 39 KiB at n = 1024, four workgroups per CU.  No floating-point atomics, fixed reduction orders:
-// the same input gives the same bits; a date never reads or writes another date's data.
+// 39 KiB at n = 1024, four workgroups per CU.  The chain adds nothing to it: the chain and the
+// merge slots live in the child arrays the merges fill later, the union-find in the place of
+// 1 / sd, the published scalars in the reduction scratch.  No floating-point atomics, fixed
+// reduction orders: the same input gives the same bits; a date never reads or writes another
+// date's data.
 #include <limits.h>
 #include <type_traits>
 
@@ -62,11 +84,29 @@ PQ_DEVFN void hrp_node(int n, int lvl, int m, int& lo, int& hi) {
   }
 }
 
-__global__ __launch_bounds__(HRP_NT) void k_hrp(
-    const double* __restrict__ S, int64_t ld, int n, const double* __restrict__ av,
-    const double* __restrict__ cv, double scale, double* __restrict__ x, int64_t ldx,
-    int32_t* __restrict__ order, int64_t ldo, double* __restrict__ link, double* __restrict__ stats,
-    int32_t* __restrict__ status) {
+// The Lance-Williams update of the distance of cluster i to the merged x and y, in the operation
+// order of SciPy's _hierarchy_distance_update.pxi (sizes as doubles, every product left to right,
+// nothing contracted: a fused multiply-add changes bits and eventually trees).
+template <int M>
+PQ_DEVFN double hrp_lance_williams(double dxi, double dyi, double dxy, int nx, int ny, int ni) {
+#pragma clang fp contract(off)
+  if constexpr (M == PQ_HRP_COMPLETE) return dxi > dyi ? dxi : dyi;
+  else if constexpr (M == PQ_HRP_AVERAGE) return ((double)nx * dxi + (double)ny * dyi) / (double)(nx + ny);
+  else if constexpr (M == PQ_HRP_WEIGHTED) return 0.5 * (dxi + dyi);
+  else {
+    const double tt = 1.0 / (double)(nx + ny + ni);
+    return sqrt((double)(ni + nx) * tt * dxi * dxi + (double)(ni + ny) * tt * dyi * dyi -
+                (double)ni * tt * dxy * dxy);
+  }
+}
+
+// One date.  M = PQ_HRP_SINGLE: Prim, and work is not touched.  Otherwise the chain on the
+// date's slab of work (read back by other threads after a barrier: not a restrict pointer).
+template <int M>
+PQ_DEVFN void hrp_date(const double* __restrict__ S, int64_t ld, int n, const double* __restrict__ av,
+                       const double* __restrict__ cv, double scale, double* __restrict__ x, int64_t ldx,
+                       int32_t* __restrict__ order, int64_t ldo, double* __restrict__ link,
+                       double* __restrict__ stats, int32_t* __restrict__ status, double* work, int64_t ldw) {
   extern __shared__ double hrp_lds[];
   const int na = hrp_slots(n);
   // persistent
@@ -144,7 +184,7 @@ __global__ __launch_bounds__(HRP_NT) void k_hrp(
   // ---- Prim ---------------------------------------------------------------------------------
   const int j0 = HRP_PER * t;
   const bool vec = (reinterpret_cast<uintptr_t>(Sb) & 15) == 0 && (ld & 1) == 0 && j0 + 3 < n;
-  {
+  if constexpr (M == PQ_HRP_SINGLE) {
     double best[HRP_PER], isdj[HRP_PER];
     unsigned done = 0;   // bit q: column j0 + q has joined (or lies past n)
 #pragma unroll
@@ -230,6 +270,197 @@ __global__ __launch_bounds__(HRP_NT) void k_hrp(
 #pragma unroll
     for (int q = 0; q < HRP_PER; ++q)
       if (j0 + q < n && j0 + q != xc && !isfinite(sv[q])) bad = 1;
+  } else {
+    // ---- the distance matrix: the upper triangle of S, mirrored ------------------------------
+    double* Wb = work + (int64_t)b * n * ldw;
+    const bool vecw = (reinterpret_cast<uintptr_t>(Wb) & 15) == 0 && (ldw & 1) == 0 && j0 + 3 < n;
+    {
+      double isdj[HRP_PER];
+#pragma unroll
+      for (int q = 0; q < HRP_PER; ++q) isdj[q] = j0 + q < n ? s_isd[j0 + q] : 0.0;
+      constexpr int RU = 4;   // rows in flight
+      for (int r0 = 0; r0 < n; r0 += RU) {
+        double sv[RU][HRP_PER];
+#pragma unroll
+        for (int u = 0; u < RU; ++u) {
+          const double* row = Sb + (int64_t)min(r0 + u, n - 1) * ld;
+          if (vec) {
+            const double2 p0 = *reinterpret_cast<const double2*>(row + j0);
+            const double2 p1 = *reinterpret_cast<const double2*>(row + j0 + 2);
+            sv[u][0] = p0.x; sv[u][1] = p0.y; sv[u][2] = p1.x; sv[u][3] = p1.y;
+          } else {
+#pragma unroll
+            for (int q = 0; q < HRP_PER; ++q) sv[u][q] = j0 + q < n ? row[j0 + q] : 0.0;   // never past column n
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < RU; ++u) {
+          const int r = r0 + u;
+          if (r >= n) break;
+          const double ix = s_isd[r];
+          double* wrow = Wb + (int64_t)r * ldw;
+#pragma unroll
+          for (int q = 0; q < HRP_PER; ++q) {
+            const int j = j0 + q;
+            if (j >= n) continue;
+            if (j == r) {
+              wrow[j] = 0.0;
+              continue;
+            }
+            if (!isfinite(sv[u][q])) bad = 1;   // every entry, though only the upper ones are used
+            if (j < r) continue;
+            const double rho = fmin(fmax((a * sv[u][q]) * (ix * isdj[q]), -1.0), 1.0);   // Prim's key: ties stay exact
+            const double dv = sqrt(0.5 * (1.0 - rho));
+            wrow[j] = dv;
+            Wb[(int64_t)j * ldw + r] = dv;
+          }
+        }
+      }
+    }
+    bad = (int)block_max((double)bad, red);   // (its barriers publish D)
+    if (bad) {   // (uniform) before the chain: it must only ever see finite numbers
+      fail();
+      return;
+    }
+
+    // ---- the nearest-neighbour chain ------------------------------------------------------------
+    u16* s_chain = s_c0;
+    u16* s_mx = s_pv;                                  // the slots of merge k, x < y
+    u16* s_my = s_end;
+    // (past the four doubles the block reductions use: a wave may still be reading those)
+    double* s_dxy = red + 4;                           // 2: D_xy of a scan, double-buffered
+    int* s_nsz = reinterpret_cast<int*>(red + 6);      // 2 x 2: the sizes of x and y, likewise
+    int* s_low = s_nsz + 4;                            // 4: the waves' lowest live columns
+    auto load_wrow = [&](int r, double (&dv)[HRP_PER]) {
+      const double* row = Wb + (int64_t)r * ldw;
+      if (vecw) {
+        const double2 p0 = *reinterpret_cast<const double2*>(row + j0);
+        const double2 p1 = *reinterpret_cast<const double2*>(row + j0 + 2);
+        dv[0] = p0.x; dv[1] = p0.y; dv[2] = p1.x; dv[3] = p1.y;
+      } else {
+#pragma unroll
+        for (int q = 0; q < HRP_PER; ++q) dv[q] = j0 + q < n ? row[j0 + q] : 0.0;
+      }
+    };
+    int sz[HRP_PER];   // the cluster in column j0 + q; 0: dead (or past n)
+#pragma unroll
+    for (int q = 0; q < HRP_PER; ++q) sz[q] = j0 + q < n ? 1 : 0;
+    const int ne = n - 1;
+    int len = 1, top = 0, prev = 0, merges = 0;   // an empty chain starts at the lowest live index
+    if (t == 0) s_chain[0] = 0;
+    for (int step = 0; step < 4 * n && merges < ne; ++step) {
+      double rv[HRP_PER];
+      load_wrow(top, rv);
+      double bv = INF;
+      int bi = INT_MAX;
+#pragma unroll
+      for (int q = 0; q < HRP_PER; ++q)
+        if (sz[q] > 0 && j0 + q != top && rv[q] < bv) {   // strict <: the lowest index among the minima
+          bv = rv[q];
+          bi = j0 + q;
+        }
+      double mv = bv;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) mv = fmin(mv, __shfl_xor(mv, o, 64));
+      const unsigned long long bal = __ballot(bi != INT_MAX && bv == mv);
+      const int src = bal ? __ffsll((long long)bal) - 1 : 0;
+      int wi = __shfl(bi, src, 64);
+      if (!bal) wi = INT_MAX;
+      const int par = step & 1;
+      if (l == 0) {
+        s_slotv[par * 4 + w] = mv;
+        s_sloti[par * 4 + w] = wi;
+      }
+      if ((top >> 2) == t) s_nsz[par * 2] = sz[top & 3];
+      if (len >= 2 && (prev >> 2) == t) {
+        s_nsz[par * 2 + 1] = sz[prev & 3];
+        s_dxy[par] = rv[prev & 3];
+      }
+      __syncthreads();
+      double gv = INF;
+      int gi = INT_MAX;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const double v2 = s_slotv[par * 4 + u];
+        const int i2 = s_sloti[par * 4 + u];
+        if (i2 != INT_MAX && v2 < gv) {
+          gv = v2;
+          gi = i2;
+        }
+      }
+      const double dxy = len >= 2 ? s_dxy[par] : INF;
+      if (!(len >= 2 && !(gv < dxy))) {
+        // a strictly nearer neighbour than the previous element: push it
+        if (gi == INT_MAX || len >= n) {   // (uniform; not with finite distances)
+          bad = 1;
+          break;
+        }
+        gi = min(max(gi, 0), n - 1);
+        if (t == 0) s_chain[len] = (u16)gi;
+        prev = top;
+        top = gi;
+        ++len;
+        continue;
+      }
+      // the previous element is the nearest: merge the two
+      const bool topx = top < prev;
+      const int mx = topx ? top : prev, my = topx ? prev : top;
+      const int nx = s_nsz[par * 2 + (topx ? 0 : 1)], ny = s_nsz[par * 2 + (topx ? 1 : 0)];
+      double pv[HRP_PER], nv[HRP_PER];
+      load_wrow(prev, pv);
+      bool any = false;
+#pragma unroll
+      for (int q = 0; q < HRP_PER; ++q) {
+        const int j = j0 + q;
+        const double dxi = topx ? rv[q] : pv[q], dyi = topx ? pv[q] : rv[q];
+        const bool upd = sz[q] > 0 && j != mx && j != my;
+        nv[q] = upd ? hrp_lance_williams<M>(dxi, dyi, dxy, nx, ny, sz[q]) : dyi;
+        if (upd) Wb[(int64_t)j * ldw + my] = nv[q];
+        any |= upd;
+      }
+      double* yrow = Wb + (int64_t)my * ldw;
+      if (vecw) {   // (the entries of dead columns are rewritten as they were)
+        if (any) {
+          *reinterpret_cast<double2*>(yrow + j0) = make_double2(nv[0], nv[1]);
+          *reinterpret_cast<double2*>(yrow + j0 + 2) = make_double2(nv[2], nv[3]);
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < HRP_PER; ++q)
+          if (sz[q] > 0 && j0 + q != mx && j0 + q != my) yrow[j0 + q] = nv[q];   // never past column n
+      }
+      if (t == 0) {
+        s_ekey[merges] = dxy;
+        s_mx[merges] = (u16)mx;
+        s_my[merges] = (u16)my;
+      }
+      if ((mx >> 2) == t) sz[mx & 3] = 0;
+      if ((my >> 2) == t) sz[my & 3] = nx + ny;
+      int lj = INT_MAX;
+#pragma unroll
+      for (int q = HRP_PER - 1; q >= 0; --q)
+        if (sz[q] > 0) lj = j0 + q;
+      const unsigned long long lbal = __ballot(lj != INT_MAX);
+      const int lw = __shfl(lj, lbal ? __ffsll((long long)lbal) - 1 : 0, 64);
+      if (l == 0) s_low[w] = lbal ? lw : INT_MAX;
+      ++merges;
+      len -= 2;
+      __syncthreads();   // publishes the new row and column y
+      if (len == 0) {
+        int low = INT_MAX;
+#pragma unroll
+        for (int u = 3; u >= 0; --u)
+          if (s_low[u] != INT_MAX) low = s_low[u];   // (waves are in column order)
+        top = min(max(low, 0), n - 1);
+        prev = top;
+        len = 1;
+        if (t == 0) s_chain[0] = (u16)top;
+      } else {
+        top = s_chain[len - 1];
+        prev = len >= 2 ? s_chain[len - 2] : top;
+      }
+    }
+    if (merges < ne) bad = 1;   // (uniform) the cap: the failure path
   }
   bad = (int)block_max((double)bad, red);
   if (bad) {   // (uniform)
@@ -266,11 +497,21 @@ __global__ __launch_bounds__(HRP_NT) void k_hrp(
   // the smallest gap between consecutive merge distances (the isd reads are long done: the
   // run arrays may take their place)
   double gap = INF;
-  for (int i = t; i + 1 < ne; i += HRP_NT) gap = fmin(gap, sqrt(0.5 * s_ekey[i + 1]) - sqrt(0.5 * s_ekey[i]));
-  for (int p = t; p < n; p += HRP_NT) {
-    s_idat[p] = s_pv[p];
-    s_start[p] = (u16)p;
-    s_end[p] = (u16)p;
+  u16* s_par = s_idat;          // the union-find of the chain's merges: parent and size of the
+  u16* s_usz = s_idat + 2 * na;   // ids below 2 n - 1 (the four u16 arrays 1 / sd leaves)
+  if constexpr (M == PQ_HRP_SINGLE) {
+    for (int i = t; i + 1 < ne; i += HRP_NT) gap = fmin(gap, sqrt(0.5 * s_ekey[i + 1]) - sqrt(0.5 * s_ekey[i]));
+    for (int p = t; p < n; p += HRP_NT) {
+      s_idat[p] = s_pv[p];
+      s_start[p] = (u16)p;
+      s_end[p] = (u16)p;
+    }
+  } else {   // (the chain recorded distances, not keys)
+    for (int i = t; i + 1 < ne; i += HRP_NT) gap = fmin(gap, s_ekey[i + 1] - s_ekey[i]);
+    for (int i = t; i < 2 * n - 1; i += HRP_NT) {
+      s_par[i] = (u16)i;
+      s_usz[i] = 1;
+    }
   }
   gap = -block_max(-gap, red);
 
@@ -278,14 +519,34 @@ __global__ __launch_bounds__(HRP_NT) void k_hrp(
   if (t == 0) {
     for (int m = 0; m < ne; ++m) {
       const int k = s_sidx[m];
-      const int sl = s_start[k], er = s_end[k + 1];
-      const int idl = s_idat[sl], idr = s_idat[k + 1];
-      s_c0[m] = (u16)min(idl, idr);
-      s_c1[m] = (u16)max(idl, idr);
-      s_cs[m] = (u16)(er - sl + 1);
-      s_idat[sl] = (u16)(n + m);
-      s_end[sl] = (u16)er;
-      s_start[er] = (u16)sl;
+      if constexpr (M == PQ_HRP_SINGLE) {
+        const int sl = s_start[k], er = s_end[k + 1];
+        const int idl = s_idat[sl], idr = s_idat[k + 1];
+        s_c0[m] = (u16)min(idl, idr);
+        s_c1[m] = (u16)max(idl, idr);
+        s_cs[m] = (u16)(er - sl + 1);
+        s_idat[sl] = (u16)(n + m);
+        s_end[sl] = (u16)er;
+        s_start[er] = (u16)sl;
+      } else {   // SciPy's label(): the roots of the recorded slots, the sizes the union-find's
+        auto find = [&](int v) {
+          int r = v;
+          while (s_par[r] != r) r = s_par[r];
+          while (s_par[v] != r) {   // path compression
+            const int up = s_par[v];
+            s_par[v] = (u16)r;
+            v = up;
+          }
+          return r;
+        };
+        const int ra = find(s_pv[k]), rb = find(s_end[k]);
+        const int cs = s_usz[ra] + s_usz[rb];
+        s_par[ra] = s_par[rb] = (u16)(n + m);
+        s_usz[n + m] = (u16)cs;
+        s_c0[m] = (u16)min(ra, rb);
+        s_c1[m] = (u16)max(ra, rb);
+        s_cs[m] = (u16)cs;
+      }
     }
     u16* s_off = s_end;   // (the runs are done)
     s_off[ne - 1] = 0;
@@ -302,7 +563,7 @@ __global__ __launch_bounds__(HRP_NT) void k_hrp(
       double* z = lb + 4 * m;
       z[0] = (double)s_c0[m];
       z[1] = (double)s_c1[m];
-      z[2] = sqrt(0.5 * s_ekey[m]);
+      z[2] = M == PQ_HRP_SINGLE ? sqrt(0.5 * s_ekey[m]) : s_ekey[m];
       z[3] = (double)s_cs[m];
     }
   }
@@ -446,22 +707,75 @@ __global__ __launch_bounds__(HRP_NT) void k_hrp(
   }
 }
 
+__global__ __launch_bounds__(HRP_NT) void k_hrp(
+    const double* __restrict__ S, int64_t ld, int n, const double* __restrict__ av,
+    const double* __restrict__ cv, double scale, double* __restrict__ x, int64_t ldx,
+    int32_t* __restrict__ order, int64_t ldo, double* __restrict__ link, double* __restrict__ stats,
+    int32_t* __restrict__ status) {
+  hrp_date<PQ_HRP_SINGLE>(S, ld, n, av, cv, scale, x, ldx, order, ldo, link, stats, status, nullptr, 0);
+}
+
+template <int M>
+__global__ __launch_bounds__(HRP_NT) void k_hrp_link(
+    const double* __restrict__ S, int64_t ld, int n, const double* __restrict__ av,
+    const double* __restrict__ cv, double scale, double* work, int64_t ldw, double* __restrict__ x, int64_t ldx,
+    int32_t* __restrict__ order, int64_t ldo, double* __restrict__ link, double* __restrict__ stats,
+    int32_t* __restrict__ status) {
+  hrp_date<M>(S, ld, n, av, cv, scale, x, ldx, order, ldo, link, stats, status, work, ldw);
+}
+
+// the host-checkable arguments the two entry points share
+static int hrp_check_args(const char* who, const double* S, int64_t ld, int32_t n, int32_t batch, const double* alpha,
+                          const double* c, double scale, const double* x, int64_t ldx, const int32_t* order,
+                          int64_t ldo, const double* stats, const int32_t* status) {
+  PQ_CHECK_ARG(S && alpha && c && x && order && stats && status, "%s: null argument", who);
+  PQ_CHECK_ARG(n >= 1 && n <= PQ_HRP_NMAX, "%s: n = %d outside [1, %d]", who, n, PQ_HRP_NMAX);
+  PQ_CHECK_ARG(batch >= 0, "%s: batch = %d < 0", who, batch);
+  PQ_CHECK_ARG(ld >= n, "%s: ld = %lld < n = %d", who, (long long)ld, n);
+  PQ_CHECK_ARG(ldx >= n && ldo >= n, "%s: ldx = %lld, ldo = %lld must be >= n = %d", who, (long long)ldx,
+               (long long)ldo, n);
+  PQ_CHECK_ARG(scale == scale, "%s: scale is NaN", who);
+  return 0;
+}
+
 }  // namespace pq
 
 extern "C" int pq_hrp_batched(const double* S, int64_t ld, int32_t n, int32_t batch, const double* alpha,
                               const double* c, double scale, double* x, int64_t ldx, int32_t* order, int64_t ldo,
                               double* link, double* stats, int32_t* status, void* stream) {
-  PQ_CHECK_ARG(S && alpha && c && x && order && stats && status, "pq_hrp_batched: null argument");
-  PQ_CHECK_ARG(n >= 1 && n <= PQ_HRP_NMAX, "pq_hrp_batched: n = %d outside [1, %d]", n, PQ_HRP_NMAX);
-  PQ_CHECK_ARG(batch >= 0, "pq_hrp_batched: batch = %d < 0", batch);
-  PQ_CHECK_ARG(ld >= n, "pq_hrp_batched: ld = %lld < n = %d", (long long)ld, n);
-  PQ_CHECK_ARG(ldx >= n && ldo >= n, "pq_hrp_batched: ldx = %lld, ldo = %lld must be >= n = %d", (long long)ldx,
-               (long long)ldo, n);
-  PQ_CHECK_ARG(scale == scale, "pq_hrp_batched: scale is NaN");
+  if (int rc = pq::hrp_check_args("pq_hrp_batched", S, ld, n, batch, alpha, c, scale, x, ldx, order, ldo, stats, status))
+    return rc;
   if (batch == 0) return 0;
   static_assert(pq::hrp_lds_bytes(PQ_HRP_NMAX) <= 48 * 1024, "the default dynamic LDS limit");
   hipLaunchKernelGGL(pq::k_hrp, dim3(batch), dim3(pq::HRP_NT), pq::hrp_lds_bytes(n), (hipStream_t)stream, S, ld, n,
                      alpha, c, scale, x, ldx, order, ldo, link, stats, status);
   PQ_CHECK_LAUNCH("pq_hrp_batched");
+  return 0;
+}
+
+extern "C" int pq_hrp_linkage_batched(const double* S, int64_t ld, int32_t n, int32_t batch, const double* alpha,
+                                      const double* c, double scale, int32_t method, double* work, int64_t ldw,
+                                      double* x, int64_t ldx, int32_t* order, int64_t ldo, double* link,
+                                      double* stats, int32_t* status, void* stream) {
+  const char* who = "pq_hrp_linkage_batched";
+  PQ_CHECK_ARG(method >= PQ_HRP_SINGLE && method <= PQ_HRP_WARD, "%s: method = %d outside [%d, %d]", who, method,
+               PQ_HRP_SINGLE, PQ_HRP_WARD);
+  if (method == PQ_HRP_SINGLE)
+    return pq_hrp_batched(S, ld, n, batch, alpha, c, scale, x, ldx, order, ldo, link, stats, status, stream);
+  if (int rc = pq::hrp_check_args(who, S, ld, n, batch, alpha, c, scale, x, ldx, order, ldo, stats, status)) return rc;
+  PQ_CHECK_ARG(work, "%s: work is NULL (only PQ_HRP_SINGLE needs none)", who);
+  PQ_CHECK_ARG(ldw >= n, "%s: ldw = %lld < n = %d", who, (long long)ldw, n);
+  if (batch == 0) return 0;
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(batch), dim3(pq::HRP_NT), pq::hrp_lds_bytes(n), (hipStream_t)stream, S, ld, n,
+                       alpha, c, scale, work, ldw, x, ldx, order, ldo, link, stats, status);
+  };
+  switch (method) {
+    case PQ_HRP_COMPLETE: launch(pq::k_hrp_link<PQ_HRP_COMPLETE>); break;
+    case PQ_HRP_AVERAGE: launch(pq::k_hrp_link<PQ_HRP_AVERAGE>); break;
+    case PQ_HRP_WEIGHTED: launch(pq::k_hrp_link<PQ_HRP_WEIGHTED>); break;
+    default: launch(pq::k_hrp_link<PQ_HRP_WARD>); break;
+  }
+  PQ_CHECK_LAUNCH(who);
   return 0;
 }

@@ -1998,12 +1998,18 @@ HRP_CHUNK_BYTES = 2 << 30   # the dense covariance buffer of hrp_weights stays b
 
 
 def hrp_weights(panel: "Panel", rows, tlen, alpha=None, c=None, centred: bool = True, scale: float = 1.0,
-                linkage: bool = False, chunk_bytes: int = HRP_CHUNK_BYTES, plan: "SlidePlan | None" = None):
-    """Hierarchical-risk-parity weights of every window (pq_hrp_batched): per date the
-    single-linkage tree of the correlation distance of Sigma = alpha S + c I (SciPy's conventions),
+                linkage: bool = False, chunk_bytes: int = HRP_CHUNK_BYTES, plan: "SlidePlan | None" = None,
+                method: str = "single"):
+    """Hierarchical-risk-parity weights of every window (pq_hrp_linkage_batched): per date the
+    tree of the correlation distance of Sigma = alpha S + c I as SciPy's linkage builds it,
     its leaves in pre-order and the recursive bisection of that order by inverse-variance cluster
-    variances; nothing is inverted or factored.  S is the window's sample covariance (Panel.cov
-    mode 0, ddof = 1; ``centred`` False: the Gram X'X, mode 1), formed per chunk of dates so that
+    variances; nothing is inverted or factored.  ``method``: 'single' (Prim's spanning tree, the
+    default), 'complete', 'average', 'weighted' or 'ward' (the nearest-neighbour chain on a
+    distance matrix in a second buffer of the chunk's size: ``chunk_bytes`` keeps sizing the
+    covariance buffer alone, so that a launch still fills the CUs, and peak memory is then
+    2 x ``chunk_bytes``); any other name raises ValueError.
+    S is the window's sample covariance (Panel.cov mode 0, ddof = 1; ``centred`` False: the
+    Gram X'X, mode 1), formed per chunk of dates so that
     the dense buffer stays under ``chunk_bytes``; one kernel launch per chunk.  ``alpha`` / ``c``:
     scalars or one value per date, defaults 1 and 0.  ``plan``: a SlidePlan of the row table where
     the caller has one (it covers the whole batch, so the batch has to fit one chunk).  At most
@@ -2014,6 +2020,9 @@ def hrp_weights(panel: "Panel", rows, tlen, alpha=None, c=None, centred: bool = 
     non-finite data) has NaN weights and order -1.  Does not synchronise."""
     lib = _lib.load()
     B, n, dev = int(rows.shape[0]), panel.n, panel.device
+    if method not in _lib.HRP_METHODS:
+        raise ValueError(f"hrp_weights: method '{method}' is not one of {', '.join(_lib.HRP_METHODS)}")
+    meth = _lib.HRP_METHODS[method]
     if not 1 <= n <= _lib.PQ_HRP_NMAX:
         raise ValueError(f"hrp_weights: n = {n} outside 1..{_lib.PQ_HRP_NMAX} (the tree of one date lives in LDS)")
     x = torch.empty((B, n), dtype=F64, device=dev)
@@ -2033,11 +2042,14 @@ def hrp_weights(panel: "Panel", rows, tlen, alpha=None, c=None, centred: bool = 
         raise ValueError("hrp_weights: a SlidePlan covers the whole batch; it needs chunk_bytes >= "
                          f"{8 * ld * ld * B} here")
     buf = torch.empty((per, ld, ld), dtype=F64, device=dev)
+    # the distance matrices of a chunk: n rows of pitch ld per date (scratch)
+    work = torch.empty((per, n, ld), dtype=F64, device=dev) if meth != _lib.PQ_HRP_SINGLE else None
     for b0 in range(0, B, per):
         b1 = min(B, b0 + per)
         S = panel.cov(rows[b0:b1], tlen[b0:b1], mode=0 if centred else 1, out=buf[:b1 - b0], plan=plan)
-        _lib.check(lib.pq_hrp_batched(_ptr(S), ld, n, b1 - b0, _ptr(alpha[b0:]), _ptr(c[b0:]), float(scale),
-                                      _ptr(x[b0:]), x.stride(0), _ptr(order[b0:]), order.stride(0),
-                                      _ptr(Z[b0:]) if linkage and n > 1 else None, _ptr(stats[b0:]),
-                                      _ptr(status[b0:]), _stream()), "pq_hrp_batched")
+        _lib.check(lib.pq_hrp_linkage_batched(_ptr(S), ld, n, b1 - b0, _ptr(alpha[b0:]), _ptr(c[b0:]), float(scale),
+                                              meth, None if work is None else _ptr(work), ld,
+                                              _ptr(x[b0:]), x.stride(0), _ptr(order[b0:]), order.stride(0),
+                                              _ptr(Z[b0:]) if linkage and n > 1 else None, _ptr(stats[b0:]),
+                                              _ptr(status[b0:]), _stream()), "pq_hrp_linkage_batched")
     return out

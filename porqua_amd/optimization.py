@@ -712,18 +712,23 @@ class RiskParity(Optimization):
 
 HRP_NAN_MESSAGE = "HierarchicalRiskParity: missing values in the return window are not supported"
 HRP_REASON = "bad input (a zero-variance asset without a ridge, a one-row window, or non-finite data)"
+HRP_LINKAGES = ("single", "complete", "average", "weighted")
 
 
 class HierarchicalRiskParity(Optimization):
-    """Hierarchical risk parity (Lopez de Prado 2016): the single-linkage tree of the correlation
-    distance sqrt((1 - rho) / 2) with SciPy's conventions, the assets in its leaf order, and the
+    """Hierarchical risk parity (Lopez de Prado 2016): the tree of the correlation distance
+    sqrt((1 - rho) / 2) as SciPy's linkage builds it, the assets in its leaf order, and the
     recursive bisection of that order, each half weighted by the other's inverse-variance cluster
     variance.  Not a QP and nothing is inverted or factored, so it is defined where the sample
     covariance is singular (more assets than window rows).  Every date is one workgroup of
     pq_hrp_batched (engine.hrp_weights) on the dense Sigma of the ``covariance`` spec: 'pearson',
     'linear_shrinkage', 'ledoit_wolf' / 'oas' (the intensity of engine.shrinkage_intensity), 'duv'
     -- the (a, c) mapping of RiskParity (covariance_window_form), as Sigma = alpha S + c I on the
-    sample covariance S.  ``linkage``: 'single' only.  At most _lib.PQ_HRP_NMAX assets.
+    sample covariance S.  ``linkage``: 'single' (Lopez de Prado's choice, the default), 'complete',
+    'average' or 'weighted', with SciPy's meaning; any other name raises NotImplementedError --
+    'ward' too, though the kernel has it: engine.hrp_weights(method='ward') reaches it --, and
+    'centroid' and 'median' are not built at all (their trees can invert).  At most
+    _lib.PQ_HRP_NMAX assets.
 
     * Of the constraints only the budget's right-hand side is used, as the sum of the weights
       (1 without a budget constraint).  Box and linear constraints are ignored -- the portfolio
@@ -738,8 +743,9 @@ class HierarchicalRiskParity(Optimization):
 
     def __init__(self, covariance: Optional[Covariance] = None, linkage: str = "single", **kwargs):
         super().__init__(**kwargs)
-        if linkage != "single":
-            raise NotImplementedError(f"HierarchicalRiskParity: linkage '{linkage}' is not implemented (only 'single')")
+        if linkage not in HRP_LINKAGES:
+            raise NotImplementedError(f"HierarchicalRiskParity: linkage '{linkage}' is not implemented (only "
+                                      + ", ".join(f"'{name}'" for name in HRP_LINKAGES) + ")")
         self.covariance = Covariance() if covariance is None else covariance
         self.linkage = linkage
 
@@ -760,7 +766,8 @@ class HierarchicalRiskParity(Optimization):
         a, c = covariance_window_form(self.covariance, panel, rows, tlen, dg)
         # Sigma = a Xc'Xc + c I = alpha S + c I on the sample covariance S = Xc'Xc / (T - 1)
         alpha = a * (tlen.to(a.dtype) - 1.0)
-        return engine.hrp_weights(panel, rows, tlen, alpha=alpha, c=c, scale=self.budget_scale(), linkage=linkage)
+        return engine.hrp_weights(panel, rows, tlen, alpha=alpha, c=c, scale=self.budget_scale(), linkage=linkage,
+                                  method=self.linkage)
 
     def solve(self) -> bool:
         from . import _lib, engine
