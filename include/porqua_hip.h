@@ -719,6 +719,51 @@ int pq_hrp_linkage_batched(const double* S, int64_t ld, int32_t n, int32_t batch
                            int64_t ldx, int32_t* order, int64_t ldo, double* link, double* stats, int32_t* status,
                            void* stream);
 
+/* The T x T window Gram of every date, G_b = Xc_b Xc_b' (Xc: date b's window, centred by mu; mu ==
+ * NULL: the uncentred X X'): the matrix whose eigenpairs carry the principal components of a
+ * window with more assets than rows (the PCA factor covariance, engine.pca_window_form).  panel,
+ * ldp, n, rows, tlen, tmax, batch, mu and mu_stride are read exactly as pq_cov_batched reads them
+ * (entries of rows[b] past tlen[b] are never read).  G is batch x ldg x ldg (date stride g_stride
+ * >= ldg^2), full symmetric, ldg a multiple of 64 and >= tmax; rows and columns from tlen[b] up to
+ * ldg are exactly zero, the padding helper_functions.sym_eig / pq_sym_eig_batched expect.  One
+ * workgroup per lower 64 x 64 tile and date on FP64 MFMA, the contraction over the n assets in
+ * chunks of 16 columns; the mean is subtracted while staging, so a large common mean does not
+ * cancel; tails (tlen and n not multiples of the tile) are masked, never read past.  No
+ * floating-point atomics: the same input gives the same bits.
+ * 1 <= tmax <= PQ_PCA_TMAX, n >= 1, ldp >= n.  The call does not synchronise; only host-checkable
+ * arguments return an error, and then nothing is launched.                                      */
+#define PQ_PCA_TMAX 1024
+int pq_window_gram_batched(const double* panel, int64_t ldp, int32_t n, const int32_t* rows, const int32_t* tlen,
+                           int32_t tmax, int32_t batch, const double* mu, int64_t mu_stride, double* G, int32_t ldg,
+                           int64_t g_stride, void* stream);
+
+/* The factor panel of the PCA covariance: for every date b and factor j < kcnt[b],
+ *   F[frow[b] + j][0..n) = s[b][j] * sum_t V_b[t][col[b][j]] (X[rows[b][t]][:] - mu_b[:]),
+ * t over the tlen[b] rows of the window.  V is batch x ldv x ldv (date stride v_stride >= ldv^2,
+ * ldv >= tmax) with the eigenvectors of the window Gram as columns, as pq_sym_eig_batched leaves
+ * them: unsorted, so col (int32, batch x kmax) names the column of factor j; s is batch x kmax;
+ * kcnt[b] in 0..kmax, and a date with kcnt[b] = 0 writes nothing.  F has row pitch ldf >= n; a
+ * row is written in full, zeros in [n, ldf).  With s_j = sqrt((1 - sigma2 / l_j) / (T - 1)) the
+ * rows are Z of Sigma = Z'Z + sigma2 I, so that the window kernels (pq_risk_parity_batched, the
+ * Gram mode of pq_cov_batched) read the PCA covariance as an uncentred window form of kcnt[b]
+ * rows.  One workgroup per 64 columns and date: a (kcnt x T)(T x n) FP64 MFMA product whose work
+ * follows kcnt, the window read once through the row table and centred while staging (mu ==
+ * NULL: uncentred).  Deterministic; a date writes the rows [frow[b], frow[b] + kcnt[b]) only, so
+ * with disjoint ranges (the caller's to provide, as is the size of F) no date touches another's.
+ * The per-date status of engine.pca_window_form: PQ_PCA_OK, or PQ_PCA_BAD_INPUT (a window of
+ * fewer than 2 rows, a non-finite Gram, more factors asked for than the window has rank,
+ * sigma2 <= 0), for which sigma2 is NaN and kcnt = 0.
+ * 1 <= kmax <= PQ_PCA_KMAX, 1 <= tmax <= PQ_PCA_TMAX, n >= 1.  The call does not synchronise;
+ * only host-checkable arguments return an error, and then nothing is launched.                 */
+#define PQ_PCA_KMAX 64
+#define PQ_PCA_OK 0
+#define PQ_PCA_BAD_INPUT 1
+int pq_window_project_batched(const double* panel, int64_t ldp, int32_t n, const int32_t* rows, const int32_t* tlen,
+                              int32_t tmax, int32_t batch, const double* mu, int64_t mu_stride, const double* V,
+                              int32_t ldv, int64_t v_stride, const int32_t* col, const double* s,
+                              const int32_t* kcnt, int32_t kmax, const int32_t* frow, double* F, int64_t ldf,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,13 @@ PQ_HRP_SINGLE, PQ_HRP_COMPLETE, PQ_HRP_AVERAGE, PQ_HRP_WEIGHTED, PQ_HRP_WARD = r
 HRP_METHODS = {"single": PQ_HRP_SINGLE, "complete": PQ_HRP_COMPLETE, "average": PQ_HRP_AVERAGE,
                "weighted": PQ_HRP_WEIGHTED, "ward": PQ_HRP_WARD}
 
-PQ_PG_RECORD = 384                   # doubles per problem of the grouped polish record
+# pq_window_gram_batched / pq_window_project_batched and engine.pca_window_form: the longest
+# window, the most factors of a date and the per-date status (include/porqua_hip.h)
+PQ_PCA_TMAX = 1024
+PQ_PCA_KMAX = 64
+PQ_PCA_OK, PQ_PCA_BAD_INPUT = range(2)
+
+PQ_PG_RECORD = 384                  # doubles per problem of the grouped polish record
 PQ_PG_PASS_SCRATCH = 123537          # doubles per slide group of the split polish window passes
 PQ_PG_PENDING, PQ_PG_DONE, PQ_PG_FALLBACK, PQ_PG_SKIP = range(4)
 PQ_PG_STATE = 3                      # record field holding the state
@@ -247,6 +253,10 @@ _EXPORTS = {
                         c_dp, c_dp, c_dp, c_dp], c_int32),
     "pq_hrp_linkage_batched": ([c_dp, c_int64, c_int32, c_int32, c_dp, c_dp, ctypes.c_double, c_int32, c_dp, c_int64,
                                 c_dp, c_int64, c_dp, c_int64, c_dp, c_dp, c_dp, c_dp], c_int32),
+    "pq_window_gram_batched": ([c_dp, c_int64, c_int32, c_dp, c_dp, c_int32, c_int32, c_dp, c_int64, c_dp, c_int32,
+                                c_int64, c_dp], c_int32),
+    "pq_window_project_batched": ([c_dp, c_int64, c_int32, c_dp, c_dp, c_int32, c_int32, c_dp, c_int64, c_dp,
+                                   c_int32, c_int64, c_dp, c_dp, c_dp, c_int32, c_dp, c_dp, c_int64, c_dp], c_int32),
 }
 
 _lib = None

@@ -11,7 +11,10 @@ DataFrame out) and computes the two-pass np.cov / DataFrame.cov() result with K1
 four masked MFMA Grams), the PD check with K2's Cholesky info and the repair with
 ``helper_functions.nearestPD``.  Beyond the reference's methods, 'ledoit_wolf' and 'oas' shrink
 towards mean(diag S) I with a data-driven intensity per window (engine.shrinkage_intensity:
-three sums over the window's T x T Gram).  ``estimate_batch`` is the batched backtest entry: all
+three sums over the window's T x T Gram), and 'pca' is the statistical factor model
+(probabilistic PCA, sklearn's PCA.get_covariance()): the top ``n_factors`` principal components
+of the window kept, the rest of the spectrum replaced by one trace-preserving noise level
+(engine.pca_window_form).  ``estimate_batch`` is the batched backtest entry: all
 rebalance dates of a device-resident panel at once, results left on the device.
 """
 from __future__ import annotations
@@ -48,12 +51,24 @@ SHRINKAGE_METHODS = ("ledoit_wolf", "oas")
 class Covariance:
     """``shrinkage_``: the intensity delta of the last ``estimate`` with a SHRINKAGE_METHODS
     method (float); ``shrinkage_batch_``: the (B,) device tensor of the last batched estimate
-    with one, None after any other method."""
+    with one, None after any other method.
+
+    method 'pca' (spec ``n_factors``: an int k, 1 <= k <= min(64, n - 1), or 'mp', the default:
+    the Marchenko-Pastur count of engine.pca_window_form): ``n_factors_`` and ``noise_variance_``
+    hold the factor count and the noise level sigma2 of the last ``estimate``;
+    ``n_factors_batch_`` / ``noise_variance_batch_`` the (B,) device tensors of the last
+    ``window_form_pca``.  The estimate is Z'Z + sigma2 I with k factor rows Z: RiskParity and
+    HierarchicalRiskParity solve on that k-row window form, the QP objectives on the dense
+    estimate (``estimate_batch_lr`` does not serve 'pca')."""
 
     def __init__(self, spec: CovarianceSpecification = None, *args, **kwargs):
         self.spec = CovarianceSpecification(*args, **kwargs) if spec is None else spec
         self.shrinkage_ = None
         self.shrinkage_batch_ = None
+        self.n_factors_ = None
+        self.noise_variance_ = None
+        self.n_factors_batch_ = None
+        self.noise_variance_batch_ = None
 
     def set_ctrl(self, *args, **kwargs) -> None:
         self.spec = CovarianceSpecification(*args, **kwargs)
@@ -68,6 +83,8 @@ class Covariance:
             covmat = cov_linear_shrinkage(X, self.spec.get("lambda_covmat_regularization"))
         elif method in SHRINKAGE_METHODS:
             covmat, self.shrinkage_ = _cov_shrunk(X, method)
+        elif method == "pca":
+            covmat, self.n_factors_, self.noise_variance_ = _cov_pca(X, self.n_factors)
         else:
             raise NotImplementedError("This method is not implemented yet")
         if self.spec.get("check_positive_definite") and not isPD(covmat):
@@ -75,6 +92,21 @@ class Covariance:
             covmat = pd.DataFrame(fixed, index=covmat.index, columns=covmat.columns) \
                 if isinstance(covmat, pd.DataFrame) else fixed
         return covmat
+
+    @property
+    def n_factors(self):
+        """The spec's ``n_factors`` of method 'pca' ('mp' where none is given)."""
+        nf = self.spec.get("n_factors")
+        return "mp" if nf is None else nf
+
+    def window_form_pca(self, panel, rows, tlen):
+        """method 'pca' for every window of the device row table: engine.pca_window_form's factor
+        form (Sigma_b = Z_b'Z_b + sigma2[b] I), the per-date factor counts and noise levels kept
+        in ``n_factors_batch_`` / ``noise_variance_batch_``."""
+        from . import engine
+        form = engine.pca_window_form(panel, rows, tlen, n_factors=self.n_factors)
+        self.n_factors_batch_, self.noise_variance_batch_ = form.tlen, form.sigma2
+        return form
 
     def _estimate_batch_pairwise(self, panel, rows, tlen, out, method):
         r = _pairwise_batch(panel, rows, tlen, out, method, self.spec.get("lambda_covmat_regularization"),
@@ -101,6 +133,9 @@ class Covariance:
         self.shrinkage_batch_ = None
         if method == "duv":
             return None, None, None, None
+        if method == "pca":
+            raise NotImplementedError("the 'pca' covariance is not a T-row window form: window_form_pca gives its "
+                                      "factor form, estimate the dense matrix")
         if method not in ("pearson", "linear_shrinkage") + SHRINKAGE_METHODS:
             raise NotImplementedError("This method is not implemented yet")
         B, n = int(rows.shape[0]), panel.n
@@ -225,6 +260,26 @@ def _cov_shrunk(X, method):
     return S, delta
 
 
+def _cov_pca(X, n_factors="mp"):
+    """(Sigma, k, sigma2) of one complete window: the dense Z'Z + sigma2 I of
+    engine.pca_window_form at batch 1."""
+    from . import _lib, engine
+    Xv = np.ascontiguousarray(X.to_numpy() if hasattr(X, "to_numpy") else X, dtype=np.float64)
+    if np.isnan(Xv).any():
+        raise ValueError("the pca covariance needs complete windows")
+    T, n = Xv.shape
+    pan = engine.Panel(Xv)
+    rows, tlen = pan.rows_to_device(np.arange(T, dtype=np.int32)[None], np.array([T], dtype=np.int32))
+    form = engine.pca_window_form(pan, rows, tlen, n_factors=n_factors)
+    if int(form.status[0].item()) != _lib.PQ_PCA_OK:
+        raise ValueError("the pca covariance: bad input (fewer than 2 rows, non-finite data, more factors than "
+                         "the window has rank, or no variance left for the noise level)")
+    S = form.dense(0).cpu().numpy()
+    if isinstance(X, pd.DataFrame):
+        S = pd.DataFrame(S, index=X.columns, columns=X.columns)
+    return S, int(form.tlen[0].item()), float(form.sigma2[0].item())
+
+
 def cov_ledoit_wolf(X):
     """Ledoit-Wolf (2004) shrinkage of the sample covariance towards mean(diag S) I with the
     intensity of sklearn's ledoit_wolf_shrinkage (applied to the ddof = 1 covariance)."""
@@ -234,3 +289,10 @@ def cov_ledoit_wolf(X):
 def cov_oas(X):
     """Oracle approximating shrinkage (Chen et al. 2010), sklearn's oas intensity."""
     return _cov_shrunk(X, "oas")[0]
+
+
+def cov_pca(X, n_factors="mp"):
+    """PCA factor covariance (probabilistic PCA, sklearn's PCA.get_covariance() with the noise
+    level averaged over n - k): the top ``n_factors`` principal components, 'mp': the
+    Marchenko-Pastur count (engine.pca_window_form)."""
+    return _cov_pca(X, n_factors)[0]

@@ -2053,3 +2053,179 @@ def hrp_weights(panel: "Panel", rows, tlen, alpha=None, c=None, centred: bool = 
                                               _ptr(Z[b0:]) if linkage and n > 1 else None, _ptr(stats[b0:]),
                                               _ptr(status[b0:]), _stream()), "pq_hrp_linkage_batched")
     return out
+
+
+PCA_CHUNK_BYTES = 2 << 30   # Gram, eigenvector and work buffers of pca_window_form stay below this
+# the eigensolver of pca_window_form where the caller names none: on the 4749 window Grams of config 3
+# (252 x 252) rocSOLVER's eigh takes 432 ms, the block-Jacobi kernels 2994 ms (profiles/pca_cov_bench.log)
+PCA_BACKEND = "rocsolver"
+
+
+class PcaWindowForm:
+    """The PCA factor covariance of every date as an uncentred window form: Sigma_b = Z_b'Z_b +
+    sigma2[b] I with Z_b the rows ``rows[b, :tlen[b]]`` of ``panel`` (engine.pca_window_form)."""
+
+    def __init__(self, panel, rows, tlen, sigma2, evals, status):
+        self.panel, self.rows, self.tlen = panel, rows, tlen
+        self.sigma2, self.evals, self.status = sigma2, evals, status
+
+    def dense(self, i: int) -> torch.Tensor:
+        """The n x n Sigma of date i (torch, on the device; NaN for a PQ_PCA_BAD_INPUT date)."""
+        Z = self.panel.R[self.rows[i, :int(self.tlen[i].item())].long()]
+        return Z.T @ Z + self.sigma2[i] * torch.eye(self.panel.n, dtype=F64, device=Z.device)
+
+
+def _row_sums_fixed(x: torch.Tensor) -> torch.Tensor:
+    """Row sums of a (B, m) tensor by a fixed binary tree of elementwise additions: a row's bits
+    do not depend on the other rows of the batch (torch.sum chooses its reduction by the shape)."""
+    W = 1 << max(0, int(x.shape[1]) - 1).bit_length()
+    if W != x.shape[1]:
+        x = torch.cat([x, x.new_zeros((x.shape[0], W - x.shape[1]))], 1)
+    while W > 1:
+        W //= 2
+        x = x[:, :W] + x[:, W:2 * W]
+    return x[:, 0]
+
+
+def _pca_eigen_map(ev, dg, tlen, n: int, kcap: int, mp: bool, finite):
+    """The eigenvalue map of pca_window_form on one chunk: from the unsorted Gram eigenvalues
+    ``ev`` (Bc, >= 1), diag(Xc'Xc) ``dg`` (Bc, n) and the window lengths, per date the factor
+    count, the noise level, l_1..l_kcap, the row scales s, the eigenvector columns and the OK
+    flag.  Sorting, elementwise operations and fixed-order sums only, so that a date's result does
+    not depend on the batch it is in."""
+    dev = ev.device
+    ssq = _row_sums_fixed(dg)
+    Tf = tlen.to(F64)
+    dof = Tf - 1.0
+    g, idx = torch.sort(ev, dim=1, descending=True)
+    W = kcap + 1
+    if g.shape[1] < W:   # l_j = 0 beyond the Gram's size
+        pad = W - g.shape[1]
+        g = torch.cat([g, torch.zeros((g.shape[0], pad), dtype=F64, device=dev)], 1)
+        idx = torch.cat([idx, torch.zeros((idx.shape[0], pad), dtype=idx.dtype, device=dev)], 1)
+    g, idx = g[:, :W], idx[:, :W]
+    l = g / dof[:, None]
+    ks = torch.arange(1, kcap + 1, device=dev)
+    cs = torch.empty((ev.shape[0], kcap), dtype=F64, device=dev)
+    acc = torch.zeros(ev.shape[0], dtype=F64, device=dev)
+    for j in range(kcap):   # (the running sum l_1 + .. + l_j in a fixed order; kcap <= PQ_PCA_KMAX)
+        acc = acc + l[:, j]
+        cs[:, j] = acc
+    sig_all = ((ssq / dof)[:, None] - cs) / (n - ks).to(F64)   # sigma2 with k kept
+    if mp:   # the smallest k whose next eigenvalue lies inside the Marchenko-Pastur bulk of its noise level
+        edge = (1.0 + torch.sqrt(n / Tf)) ** 2
+        hit = l[:, 1:W] <= edge[:, None] * sig_all
+        k_b = torch.where(hit.any(1), torch.argmax(hit.to(torch.int32), 1) + 1, kcap)
+    else:
+        k_b = torch.full((ev.shape[0],), kcap, dtype=torch.int64, device=dev)
+    sel = (k_b - 1)[:, None]
+    sig = sig_all.gather(1, sel).squeeze(1)
+    gk = g.gather(1, sel).squeeze(1)
+    ok = finite & (tlen >= 2) & (gk > Tf * 2.0 ** -52 * g[:, 0]) & (sig > 0) & torch.isfinite(sig)
+    used = (ks[None, :] <= k_b[:, None]) & ok[:, None]
+    lk = l[:, :kcap]
+    s = torch.sqrt(torch.clamp(1.0 - sig[:, None] / lk, min=0.0) / dof[:, None])
+    s = torch.where(used, s, torch.zeros_like(s)).contiguous()
+    nan = torch.full_like(sig, float("nan"))
+    evals = torch.where(used, lk, torch.zeros_like(lk))
+    evals = torch.where(ok[:, None], evals, nan[:, None])
+    kcnt = torch.where(ok, k_b, torch.zeros_like(k_b)).to(torch.int32)
+    return kcnt, torch.where(ok, sig, nan), evals, s, idx[:, :kcap].to(torch.int32).contiguous(), ok
+
+
+def pca_window_form(panel: "Panel", rows, tlen, n_factors="mp", backend: str | None = None, kmax: int = 64,
+                    chunk_bytes: int = PCA_CHUNK_BYTES) -> PcaWindowForm:
+    """The PCA factor covariance (probabilistic PCA, Tipping & Bishop; sklearn's
+    PCA.get_covariance()) of every window as a k-row window form.  With G = Xc Xc' = V diag(g) V'
+    the T x T Gram of the centred window, l_j = g_j / (T - 1) and tr S from Panel.window_sumsq,
+        sigma2 = (tr S - sum_{j<=k} l_j) / (n - k),    Z_j = sqrt((1 - sigma2 / l_j) / (T - 1)) v_j' Xc,
+        Sigma = Z'Z + sigma2 I:
+    the k largest principal components kept, the rest of the spectrum replaced by one noise level
+    that preserves the trace.  Z is written as k rows of a factor panel, so that
+    risk_parity_weights(form.panel, form.rows, form.tlen, centred=False, a=1, c=form.sigma2) and
+    hrp_weights(..., centred=False, alpha=1, c=form.sigma2) solve on Sigma as they stand.
+
+    ``n_factors``: an int k with 1 <= k <= min(kmax, n - 1), or 'mp': per date the smallest k in
+    1..kmax with l_{k+1} <= (1 + sqrt(n / T))^2 sigma2_k (the next eigenvalue inside the
+    Marchenko-Pastur bulk of the noise level with k kept; l_j = 0 beyond the Gram's size), kmax
+    where none is.  ``kmax`` <= _lib.PQ_PCA_KMAX.  ``backend``: 'jacobi' (helper_functions.sym_eig)
+    or 'rocsolver' (torch.linalg.eigh); None: PCA_BACKEND.  Per chunk of dates (Gram, eigenvectors
+    and solver work below ``chunk_bytes``): window means, pq_window_gram_batched, the
+    eigendecomposition, the eigenvalue map in a few O(T) device ops, pq_window_project_batched.
+
+    Returns a PcaWindowForm: ``panel`` (the factor rows), ``rows`` (B, kmax_used) int32, ``tlen``
+    (B,) int32 the factor count k_b, ``sigma2`` (B,), ``evals`` (B, kmax_used) the l_j kept (0
+    beyond k_b), ``status`` (B,) int32.  A date is _lib.PQ_PCA_BAD_INPUT where tlen < 2, the Gram
+    is not finite, g_k <= T 2^-52 g_1 (more factors than the window has rank) or sigma2 <= 0: its
+    sigma2 and evals are NaN and it has no factor rows (k_b = 0), so the consumers report it as
+    their own bad input; its neighbours are unaffected.  Synchronises (the size of the factor
+    panel is read back per chunk)."""
+    from .helper_functions import sym_eig
+    lib = _lib.load()
+    B, tmax = int(rows.shape[0]), int(rows.shape[1])
+    n, dev = panel.n, panel.device
+    backend = PCA_BACKEND if backend is None else backend
+    if backend not in ("jacobi", "rocsolver"):
+        raise ValueError("pca_window_form: backend must be 'jacobi' or 'rocsolver'")
+    if isinstance(kmax, bool) or not isinstance(kmax, (int, np.integer)) or not 1 <= kmax <= _lib.PQ_PCA_KMAX:
+        raise ValueError(f"pca_window_form: kmax = {kmax} outside 1..{_lib.PQ_PCA_KMAX}")
+    if n < 2:
+        raise ValueError("pca_window_form: a factor model needs at least 2 assets")
+    kcap = min(int(kmax), n - 1)
+    mp = isinstance(n_factors, str) and n_factors == "mp"
+    if not mp:
+        if (isinstance(n_factors, bool) or not isinstance(n_factors, (int, np.integer))
+                or not 1 <= n_factors <= kcap):
+            raise ValueError(f"pca_window_form: n_factors = {n_factors!r} must be 'mp' or an int in "
+                             f"1..min(kmax, n - 1) = {kcap}")
+        kcap = int(n_factors)
+    if not 1 <= tmax <= _lib.PQ_PCA_TMAX:
+        raise ValueError(f"pca_window_form: windows of up to {tmax} rows (supported: 1..{_lib.PQ_PCA_TMAX})")
+    rows = rows.contiguous()
+    ldg = round_up(tmax, 64)
+    work = int(lib.pq_sym_eig_work_doubles(ldg)) if backend == "jacobi" else 2 * ldg * ldg
+    per = max(1, min(B, int(chunk_bytes) // (8 * (2 * ldg * ldg + work))))
+    sigma2 = torch.empty(B, dtype=F64, device=dev)
+    evals = torch.empty((B, kcap), dtype=F64, device=dev)
+    kcnt = torch.empty(B, dtype=torch.int32, device=dev)
+    frow = torch.empty(B, dtype=torch.int32, device=dev)
+    G = torch.empty((min(per, B), ldg, ldg), dtype=F64, device=dev)
+    pieces, base = [], 0
+    for b0 in range(0, B, per):
+        b1 = min(B, b0 + per)
+        r, t = rows[b0:b1], tlen[b0:b1]
+        mu = panel.window_means(r, t)
+        dg = panel.window_sumsq(r, t, mu)
+        Gc = G[:b1 - b0]
+        _lib.check(lib.pq_window_gram_batched(_ptr(panel.R), panel.R.stride(0), n, _ptr(r), _ptr(t), tmax, b1 - b0,
+                                              _ptr(mu), mu.stride(0), _ptr(Gc), ldg, ldg * ldg, _stream()),
+                   "pq_window_gram_batched")
+        # a NaN or inf in the window (or in its mean) reaches the Gram's diagonal: such a date is
+        # bad input, and the eigensolver sees a zero matrix in its place
+        finite = torch.isfinite(torch.diagonal(Gc, dim1=1, dim2=2)).all(1)
+        Gc.masked_fill_(~finite[:, None, None], 0.0)
+        if backend == "jacobi":
+            ev, V = sym_eig(Gc, tmax)
+            ev, ldv = ev[:, :tmax], ldg
+        else:
+            ev, V = torch.linalg.eigh(Gc[:, :tmax, :tmax])
+            V, ldv = V.contiguous(), tmax
+        kc, sig, lk, s, col, _ = _pca_eigen_map(ev, dg[:, :n], t, n, kcap, mp, finite)
+        fr = (torch.cumsum(kc, 0, dtype=torch.int64) - kc).to(torch.int32)   # first factor row inside the chunk
+        total = int(kc.sum().item())
+        sigma2[b0:b1], evals[b0:b1], kcnt[b0:b1], frow[b0:b1] = sig, lk, kc, fr + base
+        if total:
+            F = torch.empty((total, n), dtype=F64, device=dev)
+            _lib.check(lib.pq_window_project_batched(_ptr(panel.R), panel.R.stride(0), n, _ptr(r), _ptr(t), tmax,
+                                                     b1 - b0, _ptr(mu), mu.stride(0), _ptr(V), ldv, ldv * ldv,
+                                                     _ptr(col), _ptr(s), _ptr(kc), kcap,
+                                                     _ptr(fr), _ptr(F), n, _stream()),
+                       "pq_window_project_batched")
+            pieces.append(F)
+            base += total
+    used = max(1, int(kcnt.max().item())) if B else 1
+    F = torch.cat(pieces) if len(pieces) > 1 else pieces[0] if pieces else torch.zeros((1, n), dtype=F64, device=dev)
+    j = torch.arange(used, dtype=torch.int32, device=dev)[None, :]
+    frows = torch.where(j < kcnt[:, None], frow[:, None] + j, torch.zeros_like(j)).contiguous()
+    status = torch.where(kcnt > 0, _lib.PQ_PCA_OK, _lib.PQ_PCA_BAD_INPUT).to(torch.int32)
+    return PcaWindowForm(Panel(F, device=dev), frows, kcnt, sigma2, evals[:, :used].contiguous(), status)

@@ -139,7 +139,13 @@ class EmptyOptimization(Optimization):
 
 
 class MeanVariance(Optimization):
-    """P = 2 * risk_aversion * Sigma, q = -mu_geometric (src/optimization.py:157-177)."""
+    """P = 2 * risk_aversion * Sigma, q = -mu_geometric (src/optimization.py:157-177).
+
+    With the 'pca' covariance ``set_objective`` takes the dense estimate of
+    ``Covariance.estimate`` and ``objective_batch`` returns None, so a backtest runs the serial
+    loop.  The QP window path on the factor form is deliberately not offered: its capacitance
+    would be k + mg wide, and the backtest's group plan is built from the original row table,
+    which must not be mixed with the factor rows."""
 
     batch_handles_nan = True   # windows with gaps: pairwise covariance + skipna means, batched
 
@@ -159,6 +165,8 @@ class MeanVariance(Optimization):
     def objective_batch(self, stage):
         import torch
         from . import engine
+        if self.covariance.spec["method"] == "pca":   # the dense estimate, date by date
+            return None
         nan = stage.panel.has_nan   # missing values: pairwise covariance, dense P (no window form)
         lowrank = stage.prefer_lowrank and self.covariance.spec["method"] != "duv" and not nan
         S, pdiag, mu_c, dg = self.covariance.estimate_batch_lr(
@@ -608,7 +616,11 @@ class RiskParity(Optimization):
     cyclical coordinate descent on the device (engine.risk_parity_weights, pq_risk_parity_batched)
     on the window form Sigma = a Xc'Xc + c I of the ``covariance`` spec: 'pearson' (1/(T-1), 0),
     'linear_shrinkage' c = lambda mean(diag S), 'ledoit_wolf' / 'oas' ((1-delta)/(T-1),
-    delta mean(diag S)) with the intensity of engine.shrinkage_intensity, 'duv' (0, 1).
+    delta mean(diag S)) with the intensity of engine.shrinkage_intensity, 'duv' (0, 1).  'pca':
+    the uncentred form (1, sigma2) of the k factor rows of engine.pca_window_form, built once per
+    ``solve_windows``; the per-date factor counts and noise levels stay in the covariance's
+    ``n_factors_batch_`` / ``noise_variance_batch_``, and a date whose factor model is bad input
+    (sigma2 NaN) is PQ_RP_BAD_INPUT.
 
     ``risk_budget``: a dict or Series over the assets (None: equal budgets); an asset of the
     date's selection without an entry is an error, entries must be > 0, and the budgets are
@@ -661,10 +673,18 @@ class RiskParity(Optimization):
 
     def solve_windows(self, panel, rows, tlen, universe):
         """Every window of the device row table in one launch -> (x, stats, status, form) on the
-        device; form = (mu, a, c), what risk_contributions needs."""
+        device; form = (mu, a, c), what risk_contributions needs, or (None, a, c, pca form) with
+        the 'pca' covariance: the window is then the date's factor rows."""
         from . import engine
         if panel.has_nan:
             raise ValueError(RP_NAN_MESSAGE)
+        if self.covariance.spec["method"] == "pca":
+            pf = self.covariance.window_form_pca(panel, rows, tlen)
+            a = pf.sigma2.new_ones(pf.sigma2.shape)
+            x, stats, status = engine.risk_parity_weights(
+                pf.panel, pf.rows, pf.tlen, budgets=self.budget_vector(universe), a=a, c=pf.sigma2, centred=False,
+                scale=self.budget_scale(), eps=float(self.params["eps"]), max_sweeps=int(self.params["max_sweeps"]))
+            return x, stats, status, (None, a, pf.sigma2, pf)
         mu = panel.window_means(rows, tlen)
         dg = panel.window_sumsq(rows, tlen, mu)
         a, c = self.window_form(panel, rows, tlen, dg)
@@ -676,9 +696,13 @@ class RiskParity(Optimization):
     @staticmethod
     def risk_contributions(panel, rows, tlen, form, x, i: int) -> np.ndarray:
         """x_j (Sigma x)_j / x' Sigma x of date i from the window form (torch, on the device)."""
-        mu, a, c = form
+        mu, a, c = form[:3]
+        if len(form) > 3:   # the 'pca' covariance: the uncentred factor rows of the date
+            panel, rows, tlen = form[3].panel, form[3].rows, form[3].tlen
         T = int(tlen[i].item())
-        X = panel.R[rows[i, :T].long()] - mu[i, :panel.n]
+        X = panel.R[rows[i, :T].long()]
+        if mu is not None:
+            X = X - mu[i, :panel.n]
         xi = x[i]
         m = xi * (a[i] * (X.T @ (X @ xi)) + c[i] * xi)
         return (m / m.sum()).cpu().numpy()
@@ -724,7 +748,9 @@ class HierarchicalRiskParity(Optimization):
     pq_hrp_batched (engine.hrp_weights) on the dense Sigma of the ``covariance`` spec: 'pearson',
     'linear_shrinkage', 'ledoit_wolf' / 'oas' (the intensity of engine.shrinkage_intensity), 'duv'
     -- the (a, c) mapping of RiskParity (covariance_window_form), as Sigma = alpha S + c I on the
-    sample covariance S.  ``linkage``: 'single' (Lopez de Prado's choice, the default), 'complete',
+    sample covariance S; 'pca': S the Gram Z'Z of the k factor rows of engine.pca_window_form with
+    alpha = 1 and c = sigma2 (a date whose factor model is bad input is PQ_HRP_BAD_INPUT).
+    ``linkage``: 'single' (Lopez de Prado's choice, the default), 'complete',
     'average' or 'weighted', with SciPy's meaning; any other name raises NotImplementedError --
     'ward' too, though the kernel has it: engine.hrp_weights(method='ward') reaches it --, and
     'centroid' and 'median' are not built at all (their trees can invert).  At most
@@ -761,6 +787,10 @@ class HierarchicalRiskParity(Optimization):
         from . import engine
         if panel.has_nan:
             raise ValueError(HRP_NAN_MESSAGE)
+        if self.covariance.spec["method"] == "pca":   # Sigma = Z'Z + sigma2 I on the factor rows Z
+            pf = self.covariance.window_form_pca(panel, rows, tlen)
+            return engine.hrp_weights(pf.panel, pf.rows, pf.tlen, alpha=1.0, c=pf.sigma2, centred=False,
+                                      scale=self.budget_scale(), linkage=linkage, method=self.linkage)
         mu = panel.window_means(rows, tlen)
         dg = panel.window_sumsq(rows, tlen, mu)
         a, c = covariance_window_form(self.covariance, panel, rows, tlen, dg)
