@@ -27,7 +27,9 @@ every solve takes three steps of iterative refinement on longdouble residuals.
 ``admm_woodbury_f64`` is the same iteration in float64 through the kernels' own algebra,
 K^-1 = (I - V' M^-1 V / d) / d with an explicit inverse of the capacitance M = I + V V' / d.
 Its distance from the dense model measures the rounding that algebra amplifies: it is the
-yardstick of tests/test_admm_iterates_gpu.py and nothing else.  ``admm_explicit_inverse_f64``
+yardstick of tests/test_admm_iterates_gpu.py and nothing else; ``admm_woodbury_diag_f64`` is the
+same for box rows that do not share one rho (a per-asset D; tests/test_window_mixed_gpu.py), and
+``capacitance_ref`` the capacitance M = I + U D^-1 U' itself.  ``admm_explicit_inverse_f64``
 plays the same role for the dense kernels (pq_factor_batched + pq_admm_batched,
 tests/test_dense_admm_iterates_gpu.py): float64 with an explicit K^-1 = L^-T L^-1.
 ``kkt_matrix`` is the one place K is formed (also the reference of
@@ -200,6 +202,50 @@ def admm_woodbury_f64(Xc, ps, q, Cg, lg, ug, lb, ub, rho, settings=None, iters=N
 
     return _iterate(np.asarray(q), Cg, lg, ug, lb, ub, rho, st, st.max_iter if iters is None else iters,
                     np.float64, make_solver)
+
+
+def admm_woodbury_diag_f64(Xc, ps, q, Cg, lg, ug, lb, ub, rho, settings=None, iters=None, p_diag=0.0):
+    """admm_woodbury_f64 for box rows that do NOT share one rho (a fixed variable, a free one or
+    an infinite side among ordinary ones; the kernels' "direct" capacitance, k_lr_gram): the
+    per-asset D = sigma + p_diag + rb, W = V diag(1 / sqrt(D)), M = I + W W', explicit inv(M),
+    x~ = D^-1 (rhs - V' M^-1 V D^-1 rhs).  The yardstick of tests/test_window_mixed_gpu.py."""
+    st = settings or ref_settings()
+    Xc = np.asarray(Xc, dtype=np.float64)
+    n = Xc.shape[1]
+    Cgd = np.asarray(Cg, dtype=np.float64).reshape(-1, n)
+
+    def make_solver(rg, rb, rho):
+        dinv = 1.0 / (st.sigma + p_diag + rb)
+        V = np.vstack([np.sqrt(ps) * Xc, np.sqrt(rg)[:, None] * Cgd])
+        W = V * np.sqrt(dinv)
+        Minv = np.linalg.inv(np.eye(V.shape[0]) + W @ W.T)
+        return lambda rhs: (rhs - V.T @ (Minv @ (V @ (rhs * dinv)))) * dinv
+
+    return _iterate(np.asarray(q), Cg, lg, ug, lb, ub, rho, st, st.max_iter if iters is None else iters,
+                    np.float64, make_solver)
+
+
+def capacitance_ref(Xc, ps, Cg, lg, ug, lb, ub, rho, settings=None, p_diag=0.0, tmax=None, dtype=LD):
+    """M = I + U D^-1 U' of one problem as lowrank.hip's header defines it, in ``dtype``:
+    U = [sqrt(ps) Xc (padded with zero rows to ``tmax``); sqrt(rg) Cg], k = tmax + mg rows,
+    D = sigma + p_diag + rb per asset (rb = 0 for a batch without a box, lb None); rg / rb =
+    row_rho.  Xc is taken as given (float64: the centring x - mu is the kernel's own input
+    arithmetic and is done by the caller in float64, as the kernel does it)."""
+    st = settings or ref_settings()
+    dt = np.dtype(dtype).type
+    Xc = np.asarray(Xc, dtype=np.float64)
+    T, n = Xc.shape
+    tmax = T if tmax is None else int(tmax)
+    Cgd = np.asarray(Cg, dtype=np.float64).reshape(-1, n)
+    mg = Cgd.shape[0]
+    rg = row_rho(np.reshape(lg, mg), np.reshape(ug, mg), rho, st)
+    D = np.full(n, dt(st.sigma) + dt(p_diag))
+    if lb is not None:
+        D = D + row_rho(np.reshape(lb, n), np.reshape(ub, n), rho, st).astype(dt)
+    U = np.zeros((tmax + mg, n), dtype=dt)
+    U[:T] = np.sqrt(dt(ps)) * Xc.astype(dt)
+    U[tmax:] = np.sqrt(rg.astype(dt))[:, None] * Cgd.astype(dt)
+    return np.eye(tmax + mg, dtype=dt) + (U / D) @ U.T
 
 
 def admm_explicit_inverse_f64(P, q, Cg, lg, ug, lb, ub, rho, settings=None, iters=None):

@@ -102,6 +102,10 @@ FIXED = dict(polish=0, eps_abs=1e-12, eps_rel=1e-12, eps_grouped=0.0, adapt_inte
 # ---- the kernel's inputs and state, read back from the device --------------------------------
 
 def _inputs(qb, lr, ws):
+    """The kernels' own inputs, read back.  Shared rows and a box whose rows all take one rho (the two
+    asserts): what they exclude -- fixed variables and one-sided rows among ordinary ones, per-problem
+    rows and boxes, i.e. the direct capacitance with the per-problem and the unfused grouped ADMM -- is
+    covered by tests/test_window_mixed_gpu.py."""
     n, mg, B = qb.n, qb.mg, qb.batch
     one = torch.ones(B, dtype=torch.float64, device=qb.device)
     assert qb.shared and qb.lb.shape[0] == 1

@@ -10,9 +10,9 @@ import scipy.linalg as sla
 
 from oracle.qp_ipm import solve_qp
 from porqua_amd.synthetic import factor_panel
-from tests import dense_cases
-from tests.admm_reference import (LD, _iterate, admm_dense_ref, admm_explicit_inverse_f64, admm_woodbury_f64,
-                                  kkt_matrix, ref_settings, rel_dist)
+from tests import dense_cases, window_cases
+from tests.admm_reference import (LD, _iterate, admm_dense_ref, admm_explicit_inverse_f64, admm_woodbury_diag_f64,
+                                  admm_woodbury_f64, capacitance_ref, kkt_matrix, ref_settings, rel_dist, row_rho)
 
 
 def _mean_variance(n, T, lam):
@@ -170,6 +170,97 @@ def test_explicit_inverse_model_distance_and_edges(n, centred):
     assert dense_cases.stop_edge(ref) >= 1e-3 and all(3 <= r.iters < 60 and r.status == "solved" for r in ref)
     st = engine.Settings(eps_abs=1e-12, eps_rel=1e-12, adapt_interval=4, adapt_tol=1.5, max_iter=12)
     ref, mod = dense_cases.references(case, st, rho)
+    assert dense_cases.adapt_edge(ref, st) >= 1e-3
+    assert all(r.rho != r0 and [c[0] for c in r.cands] == [4, 8] for r, r0 in zip(ref, rho))
+    assert max(abs(m.rho / r.rho - 1.0) for r, m in zip(ref, mod)) <= 1e-8
+
+
+def test_woodbury_diag_model_on_uniform_and_mixed_boxes():
+    n, T = 60, 20
+    st = ref_settings(eps_abs=1e-12, eps_rel=1e-12, adapt_interval=4, adapt_tol=1.5, max_iter=9)
+    Xc, ps, P, q, rho = _mean_variance(n, T, 1.0)
+    Cg, lg, ug = np.ones((1, n)), [1.0], [1.0]
+    lb, ub = np.zeros(n), np.full(n, 0.2)
+    a = admm_woodbury_f64(Xc, ps, q, Cg, lg, ug, lb, ub, rho, st, p_diag=1e-5)
+    b = admm_woodbury_diag_f64(Xc, ps, q, Cg, lg, ug, lb, ub, rho, st, p_diag=1e-5)
+    assert a.rho != rho and np.allclose(a.rhos, b.rhos, rtol=1e-8, atol=0.0)
+    # V V' / d against (V / sqrt(d))(V / sqrt(d))': two roundings of one algebra, each ~1e-8 from the dense model
+    # after 9 iterations with two rho changes (y of the budget row is the largest, 3e-9 apart)
+    for k in ("x", "z", "y"):
+        assert rel_dist(getattr(b, k), getattr(a, k)) <= 1e-7, k
+    # fixed at 0 and at a value, a one-sided row of each side: the uniform model refuses, the per-asset one follows
+    # the dense model
+    ub[3], lb[7], ub[7], ub[11], lb[13] = 0.0, 0.01, 0.01, np.inf, -np.inf
+    with pytest.raises(ValueError):
+        admm_woodbury_f64(Xc, ps, q, Cg, lg, ug, lb, ub, rho, st)
+    Pd = P.copy()
+    Pd[np.diag_indices(n)] += LD(1e-5)
+    r = admm_dense_ref(Pd, q, Cg, lg, ug, lb, ub, rho, st)
+    m = admm_woodbury_diag_f64(Xc, ps, q, Cg, lg, ug, lb, ub, rho, st, p_diag=1e-5)
+    assert m.iters == r.iters == 9 and [c[0] for c in m.cands] == [c[0] for c in r.cands] == [4, 8]
+    for k in ("x", "z", "y"):
+        assert rel_dist(getattr(m, k), getattr(r, k)) <= 1e-8, k
+    assert r.z[1 + 3] == 0.0 and r.z[1 + 7] == LD(0.01) and m.z[1 + 3] == 0.0 and m.z[1 + 7] == 0.01   # the fixed rows
+
+
+def test_capacitance_ref_hand_built():
+    """2 window rows padded to tmax = 3, 2 general rows (equality, unbounded), 3 assets: ordinary, fixed, free."""
+    inf = np.inf
+    st = ref_settings(sigma=1e-3, eq_scale=1e3, rho_min=1e-2)
+    X = np.array([[1.0, 2.0, -1.0], [0.5, 0.0, 3.0]])
+    Cg = np.array([[1.0, 1.0, 1.0], [2.0, 0.0, -1.0]])
+    rho, ps, pdg = 0.5, 4.0, 0.25
+    D = np.array([1e-3 + pdg + 0.5, 1e-3 + pdg + 500.0, 1e-3 + pdg + 1e-2])
+    U = np.vstack([2.0 * X, np.zeros((1, 3)), np.sqrt(500.0) * Cg[:1], np.sqrt(1e-2) * Cg[1:]])
+    want = np.eye(5) + (U / D) @ U.T
+    for dt in (LD, np.float64):
+        M = capacitance_ref(X, ps, Cg, [1.0, -inf], [1.0, inf], [0.0, 0.1, -inf], [1.0, 0.1, inf], rho, st, p_diag=pdg,
+                            tmax=3, dtype=dt)
+        assert M.dtype == dt and M.shape == (5, 5) and np.abs(M - want).max() <= 1e-12 * np.abs(want).max()
+        assert M[2, 2] == 1.0 and not M[2, :2].any() and not M[2, 3:].any()   # the padding row
+        nobox = capacitance_ref(X, ps, Cg, [1.0, -inf], [1.0, inf], None, None, rho, st, p_diag=pdg, tmax=3, dtype=dt)
+        assert np.abs(nobox - (np.eye(5) + (U / (1e-3 + pdg)) @ U.T)).max() <= 1e-9 * np.abs(nobox).max()
+    assert list(row_rho([0.0, 0.1, -inf], [1.0, 0.1, inf], rho, st)) == [0.5, 500.0, 1e-2]
+
+
+@pytest.mark.parametrize("window,kind,mg,stride", window_cases.ITER_CASES)
+def test_direct_route_model_distance(window, kind, mg, stride):
+    """The conditions tests/test_window_mixed_gpu.py::test_direct_route_iterates rests on, by the reference
+    alone: after 7 iterations the float64 per-asset-D Woodbury model is within 1e-7 of the longdouble model for
+    x, z and y on every case (so the 10 d_model bar is never looser than 1e-6) and never closer than 1e-13 (so the
+    1e-14 floor decides nothing).  Measured, worst over the 12 dates: split x 2.9e-11 .. 9.2e-11, z 5.0e-12 ..
+    4.3e-10, y 4.2e-10 .. 9.4e-10, Px 3.8e-9 .. 2.1e-8; mixed and perproblem x 1.9e-11 .. 3.1e-9, z 7.2e-12 ..
+    2.2e-9, y 3.5e-10 .. 1.4e-9, Px 1.7e-8 .. 7.8e-8 (the uncentred 282 x 150 windows the largest in x)."""
+    from porqua_amd import engine   # (Settings only: host-side defaults of rho0_rel, rho0_qrel)
+    case = window_cases.iter_case(window, kind, mg, stride)
+    st = engine.Settings(polish=0, eps_abs=1e-12, eps_rel=1e-12, adapt_interval=0, max_iter=7)
+    rho = window_cases.initial_rho(case, st)
+    ref, mod = window_cases.references(case, st, rho, 7)
+    d = {k: max(rel_dist(getattr(m, k), getattr(r, k)) for r, m in zip(ref, mod)) for k in ("x", "z", "y", "Px")}
+    print("d_model", window, kind, mg, stride, {k: "%.1e" % v for k, v in d.items()})
+    assert all(r.iters == 7 and r.status == "max_iter" for r in ref + mod)
+    assert 10.0 * max(d["x"], d["z"], d["y"]) <= 1e-6 and min(d.values()) >= 1e-13, d
+    fixed = case["lb"] == case["ub"]
+    assert fixed.any() and not fixed.all() and (case["nc"] > 1) == (kind == "perproblem")
+
+
+def test_direct_route_stop_and_adapt_edges():
+    """The one stop-count case (282 x 20 centred, per-problem rows, mg = 3) by the reference alone: with eps
+    1.6e-3, min_iter 3 no residual / eps ratio of any iteration is within 1e-3 of 1 (measured 1.18e-2; 40 .. 50
+    iterations); with interval 4, tol 1.5 every problem adapts at iterations 4 and 8, no candidate is within 1e-3 of
+    its threshold (measured 2.2e-1) and the model's rho is within 1e-8 of the reference's (2.2e-9)."""
+    from porqua_amd import engine
+    case = window_cases.iter_case(*window_cases.STOP_CASE)
+    st = engine.Settings(**window_cases.STOP)
+    rho = window_cases.initial_rho(case, st)
+    ref, _ = window_cases.references(case, st, rho, model=False)
+    edge = dense_cases.stop_edge(ref)
+    its = [r.iters for r in ref]
+    print("stop edge %.2e iterations %d..%d" % (edge, min(its), max(its)))
+    assert edge >= 1e-3 and all(r.status == "solved" for r in ref)
+    assert min(its) >= st.min_iter and max(its) < st.max_iter and len(set(its)) > 4
+    st = engine.Settings(polish=0, eps_abs=1e-12, eps_rel=1e-12, adapt_interval=4, adapt_tol=1.5, max_iter=12)
+    ref, mod = window_cases.references(case, st, rho)
     assert dense_cases.adapt_edge(ref, st) >= 1e-3
     assert all(r.rho != r0 and [c[0] for c in r.cands] == [4, 8] for r, r0 in zip(ref, rho))
     assert max(abs(m.rho / r.rho - 1.0) for r, m in zip(ref, mod)) <= 1e-8

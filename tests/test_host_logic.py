@@ -643,6 +643,27 @@ def test_lowrank_route_table():
     finally:
         engine.GCAP32_WIDE = old
     assert _route(qbw, lrw, gpw, wsw).plan is gpw.gcap_plan() is not gpw
+    # 11. shared rows, but box rows that do not share one rho -- the split box of a turnover term around a
+    #     previous portfolio at its bounds (fixed [0, 0] variables next to ordinary ones), a one-sided row, or a
+    #     free row among ordinary ones: the route of 5 (tests/test_window_mixed_gpu.py pins it on the device)
+    n11 = qb.n
+    for lo, up, uniform in ((0.0, 0.0, False), (-np.inf, np.inf, False), (0.0, np.inf, True)):
+        qb11, lr11, gp11, ws11 = _route_problem()
+        qb11.lb[0, 3:n11:5], qb11.ub[0, 3:n11:5] = lo, up
+        assert engine._uniform_box(qb11) == uniform
+        r = _route(qb11, lr11, gp11, ws11, sync_free=True)
+        if uniform:   # (a one-sided row still takes rho: the band form stays)
+            assert r.capacitance == "group"
+            continue
+        assert r.plan is gp11 and _route_fields(r) == ("direct", "grouped-unfused", "grouped", False, 0.0, 0, False)
+        assert _route_fields(_route(qb11, lr11, None, ws11)) == ("direct", "per-problem", "per-date", False, 0.0, 0, False)
+    # 12. no box at all: one D for every asset, so the band and the group capacitance stay (the window form
+    #     remains applicable: test_free_rows_and_boxless_batches_are_certified holds it to its certificate)
+    qb12, lr12, gp12, ws12 = _route_problem()
+    qb12.lb = qb12.ub = None
+    qb12.has_box = False
+    assert engine.lowrank_applicable(qb12, lr12) and engine._uniform_box(qb12)
+    assert _route_fields(_route(qb12, lr12, gp12, ws12)) == ("group", "gcap", "grouped", True, 0.5, 7, False)
 
 
 def test_workspace_declares_what_the_engine_sets():

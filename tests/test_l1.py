@@ -206,13 +206,26 @@ def test_device_backtest_turnover_budget_matches_reference():
     assert np.all(np.abs(W - g["x0"][None, :]).sum(1) <= 0.3 + 1e-7)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("shrink", [True, False])
-def test_device_backtest_window_path_transaction_cost(shrink):
+def _sparse_w0(n, ub=0.1):
+    """A long-only previous portfolio that sits at its bounds: about 80 % of the weights exactly 0
+    (= lb) and two exactly at ub; the rest positive below ub, summing to 1."""
+    rng = np.random.default_rng(9)
+    w0 = np.zeros(n)
+    held = rng.choice(n, size=n // 5, replace=False)
+    w0[held[:2]] = ub
+    w = rng.uniform(0.2, 1.0, size=held.size - 2)
+    w0[held[2:]] = (1.0 - 2 * ub) * w / w.sum()
+    assert (w0 == 0).mean() >= 0.79 and (w0 == ub).sum() == 2 and w0.max() <= ub and abs(w0.sum() - 1) < 1e-12
+    return w0
+
+
+def _window_path_l1(shrink, w0, kind, value):
     """n > window: the split runs on the Woodbury (window) path with the panel [R, -R];
-    checked against the oracle IPM on the split problem per date."""
+    checked against the oracle IPM on the split problem per date.  ``kind`` 'cost': a
+    transaction cost ``value`` around w0; 'budget': the turnover budget sum|x - w0| <= value."""
     import pandas as pd
     from porqua_amd.backtest import Backtest
+    from porqua_amd.builders import OptimizationItemBuilder
     from porqua_amd.covariance import Covariance
     from porqua_amd.optimization import MeanVariance
     from porqua_amd.synthetic import factor_panel
@@ -223,14 +236,24 @@ def test_device_backtest_window_path_transaction_cost(shrink):
     X = pd.DataFrame(R, index=idx, columns=[f"a{i}" for i in range(n)])
     y = pd.DataFrame({"bm": yv}, index=idx)
     rebdates = [str(d.date()) for d in X.index[width + 2:width + 2 + 16]]
-    w0 = np.random.default_rng(9).dirichlet(np.ones(n))
     cov = Covariance(method="linear_shrinkage", lambda_covmat_regularization=0.1) if shrink else Covariance()
-    opt = MeanVariance(covariance=cov, solver_name="mi355x", transaction_cost=0.001,
-                       x0=dict(zip(X.columns, w0)))
+    x0 = dict(zip(X.columns, w0))
+    if kind == "cost":
+        opt = MeanVariance(covariance=cov, solver_name="mi355x", transaction_cost=value, x0=x0)
+        bs = _service(opt, X, y, rebdates, width=width, box_kw={"upper": 0.1})
+    else:
+        def add_turnover(bs, rebdate, **kw):
+            bs.optimization.constraints.add_l1("turnover", rhs=value, x0=x0)
+
+        opt = MeanVariance(covariance=cov, solver_name="mi355x")
+        bs = _service(opt, X, y, rebdates, width=width, box_kw={"upper": 0.1},
+                      extra=OptimizationItemBuilder(bibfn=add_turnover))
+        bs.settings["static_builders"] = True   # the same l1 term every date: the batched path
     bt = Backtest()
-    bt.run(_service(opt, X, y, rebdates, width=width, box_kw={"upper": 0.1}))
+    bt.run(bs)
     assert bt.stats["solved"] == len(rebdates) and bt.stats["path"] == "lowrank"
     W = bt.strategy.get_weights_df().to_numpy(dtype=float)
+    tc = value if kind == "cost" else 0.0
     for i in (0, 7, len(rebdates) - 1):
         e = X.index.get_loc(pd.Timestamp(rebdates[i]))
         Xw = R[e - width + 1:e + 1]
@@ -240,16 +263,52 @@ def test_device_backtest_window_path_transaction_cost(shrink):
         P, q = 2 * S, -rp.mean_geometric(Xw, None, None, None)
         base = dict(P=P, q=q, A=np.ones((1, n)), b=np.ones(1), G=None, h=None, lb=np.zeros(n),
                     ub=np.full(n, 0.1))
-        term = L1Split("cost", w0, 0.001)
+        term = L1Split(kind, w0, value)
         sp = split_problem(base, term)
         o = solve_qp(sp["P"], sp["q"], sp["G"], sp["h"], sp["A"], sp["b"], sp["lb"], sp["ub"])
         xo, do = merge_solution(o.x, term)
-        f = lambda x: 0.5 * x @ P @ x + q @ x + 0.001 * np.abs(x - w0).sum()   # noqa: E731
+        f = lambda x: 0.5 * x @ P @ x + q @ x + tc * np.abs(x - w0).sum()   # noqa: E731
         assert abs(f(W[i]) - f(xo)) <= 1e-6 * max(abs(f(xo)), 1e-12), (i, f(W[i]), f(xo))
         assert abs(bt.stats["objective"][i] - f(W[i])) <= 1e-6 * max(abs(f(xo)), 1e-12)
         if shrink:
             assert np.abs(W[i] - xo).max() < 1e-5
         assert abs(W[i].sum() - 1) < 1e-7 and W[i].min() > -1e-7 and W[i].max() < 0.1 + 1e-7
+        if kind == "budget":
+            assert np.abs(W[i] - w0).sum() <= value + 1e-7
+    return W
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shrink", [True, False])
+def test_device_backtest_window_path_transaction_cost(shrink):
+    """A Dirichlet previous portfolio: strictly inside the box, so the split box is uniform and the
+    band form of the capacitance runs."""
+    _window_path_l1(shrink, np.random.default_rng(9).dirichlet(np.ones(200)), "cost", 0.001)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,value", [("cost", 0.001), ("budget", 0.3)])
+@pytest.mark.parametrize("shrink", [True, False])
+def test_device_backtest_window_path_sparse_previous_portfolio(monkeypatch, shrink, kind, value):
+    """The same run from a previous portfolio at its bounds (80 % of the weights exactly 0, two
+    exactly at the upper bound 0.1): the split variables of those assets are fixed, [0, 0], next to
+    ordinary ones, the box rows no longer share one rho and the solve takes the direct
+    capacitance with the unfused grouped ADMM (tests/test_window_mixed_gpu.py) -- the route of
+    every long-only backtest with a turnover term and n > T.  Same oracle, same bars; the
+    turnover budget additionally holds."""
+    from porqua_amd import engine
+    seen, solve = [], engine.solve_lowrank
+
+    def spy(*a, **kw):
+        res = solve(*a, **kw)
+        seen.append(res.capacitance)
+        return res
+
+    monkeypatch.setattr(engine, "solve_lowrank", spy)
+    w0 = _sparse_w0(200)
+    W = _window_path_l1(shrink, w0, kind, value)
+    assert seen and all(c == "direct" for c in seen), seen
+    assert (np.abs(W - w0[None, :]) > 1e-6).any()   # (it trades)
 
 
 @pytest.mark.gpu

@@ -23,6 +23,7 @@ from porqua_amd import _lib, engine
 from porqua_amd.qp_problems import QuadraticProgram, batch_result_to_solutions, solve_batch
 from porqua_amd.synthetic import factor_panel
 from tests import residual_model as rm
+from tests import window_cases as wc
 from tests.kkt import kkt_residuals
 from tests.test_polish_grouped_gpu import _problem as grouped_problem
 from tests.test_polish_wide_gpu import _problem as wide_problem
@@ -258,10 +259,61 @@ def test_dense_polish_record(device, n, variant):
 # ----------------------------------------------------------------------------------------
 
 
-@pytest.mark.parametrize("case", ["centred", "centred_ridge", "uncentred", "relaunch", "woodbury"])
+DIRECT = ("split", "mixed", "lowerside", "perproblem")   # tests/window_cases.py: the direct capacitance route
+
+
+def _direct_batch(device, variant, D=6):
+    """A 300 x 60 centred window batch whose box rows do not share one rho (or whose rows are per problem),
+    with a ridge of 5 % of mean diag P (a unique optimum for the certificate): (case, qb, lr)."""
+    kind = "mixed" if variant == "lowerside" else variant
+    case = wc.window_case(kind, 300, 60, D, 1, True, 3, ridge=0.05)
+    n, t = 300, 100
+    if variant == "lowerside":   # budget, a cap, a floor that binds (finite lg, ug = inf) and a two-sided row
+        Cg, lg, ug = case["Cg"], case["lg"], case["ug"]
+        band = np.zeros((1, 1, n))
+        band[0, 0, 2 * t:] = 1.0
+        case["Cg"] = np.concatenate([Cg, band], 1)
+        case["lg"] = np.concatenate([lg, [[0.10]]], 1)
+        case["ug"] = np.concatenate([ug, [[0.40]]], 1)
+        case["lg"][0, 2] = 0.45
+    if variant == "perproblem":
+        # the capped third without its shortable assets (lb = -inf: with them the third's net weight can be cut at
+        # no cost and the cap stays slack), capped 0.01 .. 0.02 above what its fixed variables hold: it binds in
+        # every problem (checked against the oracle IPM on the CPU: y = 2.6e-4 .. 4.4e-4)
+        for c in range(D):
+            sup = (case["Cg"][c, 1] > 0) & np.isfinite(case["lb"][c])
+            case["Cg"][c, 1] = sup.astype(float)
+            case["ug"][c, 1] = case["lb"][c][sup & (case["lb"][c] == case["ub"][c])].sum() + 0.01 + 0.002 * c
+    qb, lr, _ = wc.to_device(case, device)
+    assert not engine._band_applies(qb, lr)
+    return case, qb, lr
+
+
+def _direct_claims(variant, case, x, y, zb):
+    """What makes a direct-route case what it claims to be."""
+    c0 = 0
+    if variant == "split":
+        fixed = case["lb"][c0] == case["ub"][c0]
+        assert fixed.any() and (zb[:, fixed] != 0).any(axis=1).all()   # a fixed variable carries a multiplier
+        assert np.all(x[:, fixed] == 0.0)
+    elif variant == "mixed":
+        lo_inf, up_inf = np.isinf(case["lb"][c0]), np.isinf(case["ub"][c0])
+        fin_up = case["ub"][c0][~up_inf].max()
+        assert (x[:, lo_inf] < 0).any() or (x[:, up_inf] > fin_up).any()   # an infinite side is used
+        fixed = case["lb"][c0] == case["ub"][c0]
+        assert np.array_equal(x[:, fixed], np.broadcast_to(case["lb"][c0][fixed], x[:, fixed].shape))
+    elif variant == "lowerside":
+        assert (y[:, 2] < 0).all(), y    # the lower-sided row binds: its gap term is lg y
+    elif variant == "perproblem":
+        assert (y[:, 1] > 0).all(), y    # a cap binds in every problem
+
+
+@pytest.mark.parametrize("case", ["centred", "centred_ridge", "uncentred", "relaunch", "woodbury", *DIRECT])
 def test_window_polish_record(device, case):
     st, kcap = engine.Settings(), None
-    if case in ("centred", "centred_ridge"):
+    if case in DIRECT:
+        host_case, qb, lr = _direct_batch(device, case)
+    elif case in ("centred", "centred_ridge"):
         _, _, _, qb, lr = _mv_batch(device, 300, 60, list(range(70, 78)), 0.1, 0.05 if case == "centred_ridge" else 0.0)
     elif case == "uncentred":                       # q = -2 X'y
         qb, lr, _ = grouped_problem(device, 500, 120, 6, 0.1, centred=False)
@@ -277,6 +329,9 @@ def test_window_polish_record(device, case):
     route = f"b k_polish_w {case}"
     x, y, zb, status, out = check_records(route, Host(qb, lr), res, st)
     assert np.all(status == _lib.PQ_SOLVED), status
+    if case in DIRECT:
+        assert res.capacitance == "direct" and qb.shared == (case != "perproblem")
+        _direct_claims(case, host_case, x, y, zb)
     if kcap:
         assert ws.ldk == kcap and out[:, _lib.PQ_OUT_NFREE].min() > kcap, out[:, _lib.PQ_OUT_NFREE]
     _report(route)
@@ -344,6 +399,32 @@ def test_grouped_polish_record(device, case, mode):
     buckets = _grouped_run(device, case, mode)
     print(f"[out-record] c {case} {mode}: " + ", ".join(f"{b}: {buckets.count(b)}" for b in sorted(set(buckets))))
     _report("c k_pg_post")
+
+
+@pytest.mark.parametrize("variant", ["split", "perproblem"])
+def test_grouped_polish_record_direct_route(device, variant):
+    """The grouped pipeline behind the direct capacitance and the unfused grouped ADMM: fixed split variables
+    next to ordinary ones, and per-problem rows and boxes (Cg_stride, g_stride, box_stride != 0)."""
+    case, qb, lr = _direct_batch(device, variant)
+    gp = engine.GroupPlan(case["rows"], case["tlen"], device)
+    st = engine.Settings()
+    ws = engine.Workspace(qb, dense=False)
+    route = engine.lowrank_route(qb, lr, ws, gp, st)
+    assert (route.capacitance, route.admm, route.polish) == ("direct", "grouped-unfused", "grouped")
+    res = engine.solve_lowrank(qb, lr, st, ws=ws, groups=gp)
+    torch.cuda.synchronize()
+    assert res.capacitance == "direct"
+    rec = ws.pg_record().cpu().numpy()
+    nfree = res.out[:, _lib.PQ_OUT_NFREE].cpu().numpy()
+    buckets = [_bucket(nfree[i], rec[i, _lib.PQ_PG_STATE], rec[i, _lib.PQ_PG_W] == 1.0) for i in range(qb.batch)]
+    assert np.all((rec[:, _lib.PQ_PG_STATE] == _lib.PQ_PG_DONE) | (rec[:, _lib.PQ_PG_STATE] == _lib.PQ_PG_FALLBACK))
+    x, y, zb, status, _ = check_records(f"c direct {variant}", Host(qb, lr), res, st,
+                                        routes=[f"c k_pg_post direct {variant} " + b for b in buckets])
+    assert np.all(status == _lib.PQ_SOLVED), status
+    assert any(b != "fallback (k_polish_w)" for b in buckets), buckets   # k_pg_post scored some date
+    _direct_claims(variant, case, x, y, zb)
+    print(f"[out-record] c direct {variant}: " + ", ".join(f"{b}: {buckets.count(b)}" for b in sorted(set(buckets))))
+    _report(f"c k_pg_post direct {variant}")
 
 
 def test_grouped_cases_reach_every_scoring_route(device):
