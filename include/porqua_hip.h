@@ -102,6 +102,10 @@ typedef struct pq_settings {
    * too (0: only the wrong-sign ones) -- the next round's free set anticipates the shift, and
    * the solve's inner primal step fixes those that were right after all */
   double polish_release_rel;
+  /* pq_init_state / pq_init_state_lr: the initial rho of problem b is at least rho0_qrel *
+   * max_i |q_b[i]| (i < n), clamped to [rho_min, rho_max] (0: no floor).  For nearly linear
+   * objectives (small risk aversion) rho0_rel * mean(diag P) alone is far too small a rho */
+  double rho0_qrel;
 } pq_settings;
 
 /* Low-rank description of P for T < n (the backtest path): P_eff = p_scale[b] *

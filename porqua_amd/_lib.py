@@ -53,6 +53,8 @@ PQ_PG_PASS_SCRATCH = 123537          # doubles per slide group of the split poli
 PQ_PG_PENDING, PQ_PG_DONE, PQ_PG_FALLBACK, PQ_PG_SKIP = range(4)
 PQ_PG_STATE = 3                      # record field holding the state
 PQ_PG_K, PQ_PG_SC, PQ_PG_W = 0, 5, 320   # record fields: free count, problem scale, wide round
+# date 0's record, read as int64: 1 when the last round left a date for the host-driven repairs (R_SFLAG)
+PQ_PG_SFLAG = 366
 
 PQ_OUT_OBJ, PQ_OUT_PRIM, PQ_OUT_DUAL, PQ_OUT_GAP, PQ_OUT_RHO, PQ_OUT_NFREE, PQ_OUT_ROUNDS = range(7)
 PQ_OUT_FIELDS = 8
@@ -106,6 +108,7 @@ class PQSettings(ctypes.Structure):
         ("polish_fix_rel", ctypes.c_double),
         ("polish_inner", ctypes.c_int32), ("min_iter", ctypes.c_int32),
         ("polish_release_rel", ctypes.c_double),
+        ("rho0_qrel", ctypes.c_double),
     ]
 
 

@@ -549,9 +549,9 @@ __global__ void k_init_state(pq_problem pb, pq_state st, const int32_t* idx, pq_
     st.z[(int64_t)b * st.m_ld + i] = 0.0;
     st.y[(int64_t)b * st.m_ld + i] = 0.0;
   }
+  __shared__ double red[16];
   double rho0 = s.rho0;
   if (s.rho0_rel > 0.0) {
-    __shared__ double red[16];
     const double* P = pb.P + (int64_t)b * pb.P_stride;
     const double ps = pb.p_scale ? pb.p_scale[b] : 1.0;
     const double pd = pb.p_diag ? pb.p_diag[b] : 0.0;
@@ -565,6 +565,20 @@ __global__ void k_init_state(pq_problem pb, pq_state st, const int32_t* idx, pq_
     sdiag = block_sum(sdiag, red);
     const double md = sdiag / pb.n;
     rho0 = (md > 0.0 && isfinite(md)) ? fmin(fmax(s.rho0_rel * md, s.rho_min), s.rho_max) : s.rho0;
+  }
+  // the |q| floor: rho >= rho0_qrel * max_i |q_i| over i < n (the padding [n, ld) is not read),
+  // clamped to [rho_min, rho_max]; a NaN in q gives a NaN rho (fmax alone would drop it)
+  if (s.rho0_qrel > 0.0 && pb.q) {
+    const double* q = pb.q + (int64_t)b * pb.q_stride;
+    double qm = 0.0, qnan = 0.0;
+    for (int i = threadIdx.x; i < pb.n; i += blockDim.x) {
+      const double v = q[i];
+      qm = fmax(qm, fabs(v));
+      if (v != v) qnan = 1.0;
+    }
+    qm = block_max(qm, red);
+    qnan = block_max(qnan, red);
+    rho0 = qnan > 0.0 ? __builtin_nan("") : fmin(fmax(fmax(rho0, s.rho0_qrel * qm), s.rho_min), s.rho_max);
   }
   if (threadIdx.x == 0) {
     st.rho[b] = rho0;

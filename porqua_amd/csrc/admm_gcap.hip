@@ -84,9 +84,58 @@ __device__ __forceinline__ double band_at(const double* band, int64_t ldo, int r
 }
 
 // ---- assemble M_U (lower 64-tiles, diagonal tiles in full; identity padding) -----------
+// element (i, j) of M_U; s_w: the union rows relative to r0 (entries i and j when below U),
+// s_sr: sqrt(R) of the general rows, a1 = c / d, a2 = sqrt(c) / d
+__device__ __forceinline__ double gcap_m_elem(int i, int j, int U, int mg, const int* s_w, const double* s_sr,
+                                              double a1, double a2, double d, const double* band, int64_t ldo,
+                                              const double* pc, int64_t ldpc, const double* cc) {
+  double v = (i == j) ? 1.0 : 0.0;
+  const bool icg = i >= U && i < U + mg;
+  const bool jcg = j >= U && j < U + mg;
+  if (i < U && j < U) v += a1 * band_at(band, ldo, s_w[i], s_w[j]);
+  else if (icg && j < U) v += a2 * s_sr[i - U] * pc[(int64_t)s_w[j] * ldpc + (i - U)];
+  else if (i < U && jcg) v += a2 * s_sr[j - U] * pc[(int64_t)s_w[i] * ldpc + (j - U)];
+  else if (icg && jcg) v += s_sr[i - U] * s_sr[j - U] / d * cc[(i - U) * mg + (j - U)];
+  return v;
+}
+
+// One workgroup per (group, lower 64 x 64 tile): k_ld = 320 gives 15 tiles per group, so the 250
+// groups of config 3 are 3750 workgroups of 16 independent rows per wave instead of 250 whose
+// waves walk 80 whole rows each, one load round trip per row (latency bound at ~1.3 TB/s of
+// stores).  The tiles of one group are balanced, unlike its 64-row blocks (1 .. 5 tiles)
 __global__ __launch_bounds__(256) void k_gcap_assemble(pq_lowrank lr, pq_problem pb, pq_gcap gc, pq_settings s,
                                                        const double* band, int64_t ldo, int r0, const double* pc,
                                                        int64_t ldpc, const double* cc) {
+  __shared__ int s_w[CU_MAX];   // (only the tile's rows and columns are filled)
+  __shared__ double s_sr[CMGW];
+  const int k_ld = gc.k_ld, nb = k_ld / TB, nt = nb * (nb + 1) / 2;
+  const int grp = blockIdx.x / nt;
+  int rb = 0, cb = blockIdx.x - grp * nt;   // tile (rb, cb), cb <= rb, row-major over the lower triangle
+  while (cb > rb) cb -= ++rb;
+  const int d0 = gc.gdates[grp];
+  const int U = gc.ucnt[grp], mg = pb.mg;
+  const int t = threadIdx.x, w = wave_id(), l = lane_id();
+  if (t < 2 * TB) {
+    const int u = (t < TB ? rb * TB : cb * TB - TB) + t;
+    if (u < U) s_w[u] = gc.urows[(int64_t)grp * gc.umax + u] - r0;
+  }
+  const GConst g = gconst(lr, pb, s, d0, gc.grho[grp]);
+  if (t < mg) s_sr[t] = sqrt(row_rho(pb.lg[t], pb.ug[t], g.rho, s));
+  __syncthreads();
+  const double a1 = g.c / g.d, a2 = g.sqc / g.d;
+  double* M = gc.M + (int64_t)grp * gc.M_stride;
+  const int j = cb * TB + l;
+#pragma unroll 4
+  for (int r = 0; r < TB / 4; ++r) {
+    const int i = rb * TB + w + 4 * r;
+    M[(int64_t)i * k_ld + j] = gcap_m_elem(i, j, U, mg, s_w, s_sr, a1, a2, g.d, band, ldo, pc, ldpc, cc);
+  }
+}
+
+// the earlier form, one workgroup per group whose waves walk whole rows (PQ_GCAP_ASSEMBLE_OLD = 1: A/B)
+__global__ __launch_bounds__(256) void k_gcap_assemble_rows(pq_lowrank lr, pq_problem pb, pq_gcap gc, pq_settings s,
+                                                            const double* band, int64_t ldo, int r0,
+                                                            const double* pc, int64_t ldpc, const double* cc) {
   __shared__ int s_w[CU_MAX];
   __shared__ double s_sr[CMGW];
   const int grp = blockIdx.x;
@@ -101,16 +150,8 @@ __global__ __launch_bounds__(256) void k_gcap_assemble(pq_lowrank lr, pq_problem
   double* M = gc.M + (int64_t)grp * gc.M_stride;
   for (int i = w; i < k_ld; i += 4) {
     const int jend = (i / TB + 1) * TB;
-    const bool icg = i >= U && i < U + mg;
-    for (int j = l; j < jend; j += 64) {
-      double v = (i == j) ? 1.0 : 0.0;
-      const bool jcg = j >= U && j < U + mg;
-      if (i < U && j < U) v += a1 * band_at(band, ldo, s_w[i], s_w[j]);
-      else if (icg && j < U) v += a2 * s_sr[i - U] * pc[(int64_t)s_w[j] * ldpc + (i - U)];
-      else if (i < U && jcg) v += a2 * s_sr[j - U] * pc[(int64_t)s_w[i] * ldpc + (j - U)];
-      else if (icg && jcg) v += s_sr[i - U] * s_sr[j - U] / g.d * cc[(i - U) * mg + (j - U)];
-      M[(int64_t)i * k_ld + j] = v;
-    }
+    for (int j = l; j < jend; j += 64)
+      M[(int64_t)i * k_ld + j] = gcap_m_elem(i, j, U, mg, s_w, s_sr, a1, a2, g.d, band, ldo, pc, ldpc, cc);
   }
 }
 
@@ -1393,8 +1434,18 @@ extern "C" int pq_gcap_assemble(const pq_lowrank* lr, const pq_problem* pb, cons
   if (gcap_check(lr, pb, gc, "pq_gcap_assemble")) return -1;
   PQ_CHECK_ARG(s && band && gc->M, "pq_gcap_assemble: null argument");
   PQ_CHECK_ARG(pb->mg == 0 || (pc && cc), "pq_gcap_assemble: general rows need pc and cc");
-  hipLaunchKernelGGL(pq::k_gcap_assemble, dim3(gc->ngroups), dim3(256), 0, (hipStream_t)stream, *lr, *pb, *gc, *s,
-                     band, ldo, r0, pc, ldpc, cc);
+  // PQ_GCAP_ASSEMBLE_OLD = 1: the one-workgroup-per-group form (A/B; the same M_U bit for bit)
+  static const int old_form = [] {
+    const char* e = getenv("PQ_GCAP_ASSEMBLE_OLD");
+    return e ? atoi(e) : 0;
+  }();
+  const int nb = gc->k_ld / 64;
+  if (old_form > 0)
+    hipLaunchKernelGGL(pq::k_gcap_assemble_rows, dim3(gc->ngroups), dim3(256), 0, (hipStream_t)stream, *lr, *pb, *gc,
+                       *s, band, ldo, r0, pc, ldpc, cc);
+  else
+    hipLaunchKernelGGL(pq::k_gcap_assemble, dim3(gc->ngroups * (nb * (nb + 1) / 2)), dim3(256), 0, (hipStream_t)stream,
+                       *lr, *pb, *gc, *s, band, ldo, r0, pc, ldpc, cc);
   PQ_CHECK_LAUNCH("pq_gcap_assemble");
   return 0;
 }

@@ -28,7 +28,12 @@ enum : int {
   // sets <= 48, 64, 80, 96, 128, and PG_BIGB: the large free sets of k_pg_big); date 0's record
   // holds the counts at R_CNT (as 64-bit integers, appended by k_pg_form's atomics, cleared by
   // k_pg_post<0>)
-  R_LIST = 352, R_CNT = 360
+  R_LIST = 352, R_CNT = 360,
+  // date 0's record, a 64-bit integer: 1 when the last round left a date for the host-driven
+  // repairs (state PENDING or FALLBACK, or status NEED_REFACTOR / SOLVED_INACCURATE / UNSOLVED),
+  // else 0; cleared by k_pg_setup's block 0, set by k_pg_post<1>: the engine's sync-free flag
+  // (PQ_PG_SFLAG in _lib.py)
+  R_SFLAG = 366
 };
 constexpr int PG_NBUCKET = 6;
 constexpr int PG_BIGB = 5;
@@ -52,7 +57,8 @@ constexpr int PG_MGMAX = 32;   // general rows
 // variables as bordered rows (at most PG_WMB of them)
 constexpr int PG_WMB = 8;
 constexpr int PG_WG_MAX = 24;   // general rows of the wide mode
-static_assert(R_FXL + PG_WMB <= R_GFORM && R_KB < R_LIST && R_LIST + 6 <= R_CNT && R_CNT + 6 <= PQ_PG_RECORD,
+static_assert(R_FXL + PG_WMB <= R_GFORM && R_KB < R_LIST && R_LIST + 6 <= R_CNT && R_CNT + 6 <= R_SFLAG &&
+                  R_SFLAG < PQ_PG_RECORD,
               "PQ_PG_RECORD too small");
 
 struct PGWork {   // per-date work layout: xs | xb | g | Px | Fl | rF | solx | pxb | U | fl

@@ -134,6 +134,8 @@ __global__ __launch_bounds__(PT) void k_pg_setup(pq_problem pb, pq_state st, dou
   __shared__ double red[16];
   const int b = blockIdx.x;
   double* R = rec + (int64_t)b * PGR;
+  // the first kernel of a round: no date is left for the host yet (k_pg_post<1> sets the field)
+  if (b == 0 && threadIdx.x == 0) *reinterpret_cast<unsigned long long*>(rec + R_SFLAG) = 0ull;
   if (R[R_STATE] != PQ_PG_PENDING) return;   // uniform
   const int n = pb.n, ld = pb.ld, mg = pb.mg;
   const int t = threadIdx.x, w = wave_id(), l = lane_id();
@@ -2130,6 +2132,18 @@ __global__ __launch_bounds__(PPT) void k_pg_post(pq_lowrank lr, pq_problem pb, p
   double* R = rec + (int64_t)b * PGR;
   if (MODE == 0 && b == 0 && threadIdx.x < PG_NBUCKET)   // this round's solve-bucket lists start empty
     reinterpret_cast<unsigned long long*>(rec + R_CNT)[threadIdx.x] = 0ull;
+  // MODE 1 is the last kernel of a round to write a state or a status: a date still left for the
+  // host-driven repairs when it ends sets R_SFLAG (dates not pending here; the rejected ones below
+  // -- they stay pending or are handed back; an accepted date ends DONE and SOLVED).  A plain
+  // store of the same 1 by every such date, read by a later kernel: counting them with an atomic
+  // add (a first round rejects all 4749 dates) made the kernel 10 us longer per round, also when a
+  // date that read the field set skipped the add (profiles/r08_glue_ab_summary.txt)
+  auto left_for_host = [&]() { *reinterpret_cast<unsigned long long*>(rec + R_SFLAG) = 1ull; };
+  if (MODE == 1 && R[R_STATE] != PQ_PG_PENDING && threadIdx.x == 0) {
+    const int stt = st.status[b];
+    if (R[R_STATE] == PQ_PG_FALLBACK || stt == PQ_NEED_REFACTOR || stt == PQ_SOLVED_INACCURATE || stt == PQ_UNSOLVED)
+      left_for_host();
+  }
   if (!(R[R_STATE] == PQ_PG_PENDING && (MODE == 1 || R[R_NZB] != 0.0))) return;
   int lo = 0, hi = ngroups;   // group of date b: gdates[grp] <= b < gdates[grp + 1]
   while (hi - lo > 1) {
@@ -2267,6 +2281,7 @@ __global__ __launch_bounds__(PPT) void k_pg_post(pq_lowrank lr, pq_problem pb, p
   }
   if (bad) {
     if (hl == 0 && R[R_ROUNDS] >= s.polish_rounds) R[R_STATE] = PQ_PG_FALLBACK;
+    if (hl == 0) left_for_host();
     return;
   }
   // ---- accepted: score the polished point (polish_w.hip's final block) ------------------
@@ -2540,7 +2555,9 @@ extern "C" int pq_polish_grouped_round(const pq_lowrank* lr, const pq_problem* p
   }
   // (side stream 1: the streams are dealt round-robin over the process's hardware queues, four
   // by default, so stream 0 shared one with the <= 128 bucket's stream 4 and the register
-  // solve waited for that kernel to finish)
+  // solve waited for that kernel to finish.  On the caller's stream instead -- no fork and join
+  // around the critical path of the later rounds -- the replayed step's polish stage was 2.58-2.67 ms
+  // against a steady 2.63-2.65 ms here, the eager one 2.86-2.94 against 2.96-3.00 ms: DESIGN.md §7)
   if (nrt > 0 && pq_pg_solve_rt_launch(nrt + 2, B, on(1), pb, st, rec, s, ldk)) return -1;
   if (wide && pq_pg_wide_launch(lr, pb, st, rec, s, wide, on(5))) return -1;   // free sets beyond kmax
   for (int i = 0; side && i < pq::PgSide::NS; ++i)

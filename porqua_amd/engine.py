@@ -77,8 +77,10 @@ class Settings:
     # problems whose polish is rejected are polished again with this many refinement steps
     # (nearly singular P_FF, e.g. small risk aversions) before the ADMM retry (host-side)
     refine_retry: int = 4
-    # window path: initial rho >= rho0_qrel * max|q| (host-side, not in pq_settings): for
-    # nearly linear objectives (small risk aversion) 4 mean(diag P) is far too small a rho
+    # initial rho >= rho0_qrel * max|q|: for nearly linear objectives (small risk aversion) 4
+    # mean(diag P) is far too small a rho.  to_c() leaves pq_settings.rho0_qrel at 0: only the
+    # init call of solve / solve_lowrank passes it (k_init_state then applies the floor), so
+    # every other caller of the init entry points keeps its rho
     rho0_qrel: float = 10.0
     # wide rounds of the grouped polish (polish_gw.hip, host-side): refinement steps per round
     # (early exit at the 1e-13 residual) and the group capacitance's diagonal relative to the
@@ -186,7 +188,8 @@ class Settings:
         return s
 
 
-_C_SETTINGS = tuple(c[0] for c in _lib.PQSettings._fields_ if c[0] in Settings.__dataclass_fields__)   # (not host-side)
+_C_SETTINGS = tuple(c[0] for c in _lib.PQSettings._fields_
+                    if c[0] in Settings.__dataclass_fields__ and c[0] != "rho0_qrel")   # (not host-side)
 
 
 # ----------------------------------------------------------------------------------------
@@ -503,8 +506,9 @@ def solve(qb: QPBatch, settings: Settings | None = None, ws: Workspace | None = 
     st = ws.c_struct()
     strm = _stream()
     P_, S_, SS = ctypes.byref(pb), ctypes.byref(st), ctypes.byref(s)
-    _lib.check(lib.pq_init_state(P_, S_, None, 0, SS, strm), "pq_init_state")
-    _rho_floor_q(qb, ws, settings)
+    s_init = _init_settings(settings)
+    _lib.check(lib.pq_init_state(P_, S_, None, 0, ctypes.byref(s_init), strm), "pq_init_state")
+    _rho_floor_q(qb, ws, settings, in_kernel=s_init.rho0_qrel > 0)
     _lib.check(tl("factor", lambda: lib.pq_factor_batched(P_, S_, None, 0, SS, 1, strm)),
                "pq_factor_batched")
     cnt = {"refactors": 0, "launches": 0}
@@ -551,12 +555,29 @@ def _batch_result(qb: "QPBatch", ws: "Workspace", **counts) -> BatchResult:
                        status=ws.status, iters=ws.iters, out=ws.out, **counts)
 
 
-def _rho_floor_q(qb: "QPBatch", ws: "Workspace", settings: Settings):
-    """Initial rho >= rho0_qrel * max|q| per problem (both paths, before the first factor)."""
-    if settings.rho0_qrel > 0:
+def _init_settings(settings: Settings) -> _lib.PQSettings:
+    """The settings of the init call of solve / solve_lowrank: with pq_settings.rho0_qrel, so that
+    k_init_state applies the |q| floor of the initial rho (every other call leaves the field at 0)."""
+    return settings.to_c(rho0_qrel=0.0 if RHO_FLOOR_HOST else max(float(settings.rho0_qrel), 0.0))
+
+
+def _rho_floor_q(qb: "QPBatch", ws: "Workspace", settings: Settings, in_kernel: bool = False):
+    """Initial rho >= rho0_qrel * max|q| per problem (both paths, before the first factor).
+    ``in_kernel``: the init call carried pq_settings.rho0_qrel, so k_init_state has stored the
+    same values already and nothing is launched here."""
+    if settings.rho0_qrel > 0 and not in_kernel:
         qinf = qb.q[:, :qb.n].abs().amax(1)
         torch.clamp(torch.maximum(ws.rho, settings.rho0_qrel * qinf), settings.rho_min, settings.rho_max,
                     out=ws.rho)
+
+
+def sf_flag_torch(rec: torch.Tensor, status: torch.Tensor) -> torch.Tensor:
+    """The sync-free flag from the grouped polish's record and the status vector: any date pending, handed
+    back, rejected or unsolved, or an ADMM refactor requested (what k_pg_post notes at PQ_PG_SFLAG)."""
+    st_pg = rec[:, _lib.PQ_PG_STATE]
+    return ((st_pg == _lib.PQ_PG_PENDING) | (st_pg == _lib.PQ_PG_FALLBACK) |
+            (status == _lib.PQ_NEED_REFACTOR) | (status == _lib.PQ_SOLVED_INACCURATE) |
+            (status == _lib.PQ_UNSOLVED)).any()
 
 
 def _repolish_set(ws: "Workspace", settings: Settings):
@@ -1213,13 +1234,15 @@ class _LowRankSolve:
         self.pg_start(False)
         for _ in range(min(int(self.sf_rounds or rounds), rounds)):
             self.pg_round()
-        st_pg = self.pg["rec"][:, _lib.PQ_PG_STATE]
-        flag = ((st_pg == _lib.PQ_PG_PENDING) | (st_pg == _lib.PQ_PG_FALLBACK) |
-                (ws.status == _lib.PQ_NEED_REFACTOR) | (ws.status == _lib.PQ_SOLVED_INACCURATE) |
-                (ws.status == _lib.PQ_UNSOLVED)).any()
         if ws._sf_flag is None:
             ws._sf_flag = torch.zeros((), dtype=torch.bool, device=ws.device)
-        ws._sf_flag.copy_(flag)
+        rec = self.pg["rec"]
+        if self.pg["rounds"] > 0 and not SF_FLAG_HOST:
+            # the last round's k_pg_post noted the dates left for the host (pg_record.h, R_SFLAG): one launch
+            left = rec[0, _lib.PQ_PG_SFLAG:_lib.PQ_PG_SFLAG + 1].view(torch.int64)[0]
+            torch.ne(left, 0, out=ws._sf_flag)
+        else:   # no round ran: nothing has counted
+            ws._sf_flag.copy_(sf_flag_torch(rec, ws.status))
         return dict(self.pg)
 
     def pg_finish(self):
@@ -1282,8 +1305,9 @@ def solve_lowrank(qb: QPBatch, lr: LowRank, settings: Settings | None = None,
     ws.gcap_groups = route.plan if route.admm == "gcap" else None
     ws.sweep_admm = sweep if route.admm == "sweep" else None
     ws.pg_fallback = None
-    _lib.check(c.lib.pq_init_state_lr(*c.LPS, None, 0, c.SS, c.strm), "pq_init_state_lr")
-    _rho_floor_q(qb, ws, settings)
+    s_init = _init_settings(settings)
+    _lib.check(c.lib.pq_init_state_lr(*c.LPS, None, 0, ctypes.byref(s_init), c.strm), "pq_init_state_lr")
+    _rho_floor_q(qb, ws, settings, in_kernel=s_init.rho0_qrel > 0)
     if band:
         c.bd = tl("gram", lambda: _band_setup(qb, lr, c.strm, w_min=route.band_wmin))
     ws.band_shape = (c.bd["nrows"], c.bd["W"]) if c.bd is not None else None   # (the bench's gram rate)
@@ -1457,6 +1481,11 @@ GCAP_FACTOR = os.environ.get("PQ_GCAP_FACTOR", "batched")   # (A/B) "large": K2L
 GROUP_MAX_UNION = 320    # union rows per group (admm_grp.hip UMAXG)
 
 
+# (A/B) PQ_RHO_FLOOR_HOST=1: the |q| floor of the initial rho by torch after the init kernel (_rho_floor_q)
+# instead of inside it; PQ_SF_FLAG_HOST=1: the sync-free flag by the torch expression (sf_flag_torch)
+# instead of from the polish's own count
+RHO_FLOOR_HOST = os.environ.get("PQ_RHO_FLOOR_HOST", "0") != "0"
+SF_FLAG_HOST = os.environ.get("PQ_SF_FLAG_HOST", "0") != "0"
 SWEEP_ADMM = os.environ.get("PQ_SWEEP_ADMM", "1") != "0"   # (A/B) 0: the sweep's groups on k_admm_grp
 
 
