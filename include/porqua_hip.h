@@ -382,7 +382,8 @@ typedef struct pq_gcap {
   double* hinv; int32_t ldh;                                   /* per date: ldh x ldh      */
   int32_t gmax;                 /* dates in the largest group: 0..16 -> 16-date kernels;
                                    17..32 -> the 32-date form (one 512-thread workgroup per
-                                   group; register-resident or column-sparse general rows) */
+                                   group; register-resident or column-sparse general rows),
+                                   17..20 with mg <= 4 its tail form (pq_gcap_form)          */
 } pq_gcap;
 int pq_gcap_assemble(const pq_lowrank* lr, const pq_problem* pb, const pq_gcap* gc, const pq_settings* s,
                      const double* band, int64_t ldo, int32_t r0, const double* pc, int64_t ldpc,
@@ -393,6 +394,11 @@ int pq_gcap_prepare(const pq_lowrank* lr, const pq_problem* pb, pq_state* st, co
 int pq_admm_lr_gcap(const pq_lowrank* lr, const pq_problem* pb, pq_state* st, const pq_gcap* gc,
                     const pq_settings* s, int32_t iters_this_call, const double* pc, int64_t ldpc, int32_t r0,
                     const double* cc, const int32_t* cg_nzr, const double* cg_nzv, int32_t nzmax, void* stream);
+/* The form pq_admm_lr_gcap launches for a plan with gmax dates in its largest group and mg
+ * general rows: 1 = 16-date, 2 = 32-date with both column blocks on the MFMA, 3 = the tail
+ * form (gmax 17..20, mg <= 4: the dates past 16 on the vector pipe).  PQ_GCAP_TAIL=0 in the
+ * environment forces 2 instead of 3; it is read on every call. */
+int pq_gcap_form(int32_t gmax, int32_t mg);
 
 /* K2, eigen form (the risk-aversion x date sweep, BASELINE configs[4]): M_b^-1 of every
  * problem b (or idx[0..nidx)) of the window path from ONE symmetric eigendecomposition per

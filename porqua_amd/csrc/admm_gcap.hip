@@ -524,7 +524,31 @@ __global__ __launch_bounds__(PT_PREP, 2 / NB) void k_gcap_prep(pq_lowrank lr, pq
 // the 256-thread, 16-date form (two workgroups per CU).  The wide form runs NB = 2 as well:
 // its per-(date, row) LDS (g_part) is indexed by the date within its wave's column block, so
 // k_admm_gcap<CMGW, 2> fits the CU's 160 KiB.
-template <int MGC, int NB>
+//
+// TL = 1 (with NB = 2): the TAIL form for groups of 17 .. 16 + CRT dates (config 3's
+// CU-balanced groups have 19).  With both blocks on the MFMA, pass 2 splits its waves by column
+// block: waves 4-7 read the whole union a second time and issue block 0's MFMA count for 3 live
+// columns of 16, and the epilogue of 16 dates falls on waves 0-3 alone.  In the tail form all
+// eight waves of pass 2 walk asset blocks; a wave's union-row pairs feed block 0's two MFMAs
+// and, on the vector pipe, two fma() per tail date with Ut[u][16 + d] (one LDS address per k
+// group: a broadcast).  After the u loop the four k groups' partials are summed over lanes l,
+// l^16, l^32, l^48 in a fixed order and lane group kq owns tail date 16 + kq as a fifth slot of
+// the unchanged per-date epilogue; g_part is indexed (wave, date of the group) and reduced
+// over all eight waves in wave order.  WU / Ut keep their 32 columns (columns 16 + r .. 31
+// stay zero), and the setup, the GEMM, the Woodbury phase and the residual step are those of
+// NB = 2.  Every date's mu.V partial is summed in another order than in the MFMA form (and the
+// tail dates' pass-2 sums): the same iterates to rounding, not bit for bit.
+// Pass 1 stays on the MFMA for both column blocks: its tail form (PQ_GCAP_TAIL_P1 = 1 -- lane
+// (row l & 15, k pair l >> 4) multiplies the MFMA's A pair by each tail date's V pair and the
+// k-pair partials are summed after the k loop) halves pass 1's MFMAs but measured slower, 0.94
+// against 0.86 ms of phase clock at config 3: pass 1 streams the union at
+// the rate L2 / MALL delivers it, and four more V loads and 32 FP64 vector instructions per
+// k step cost more than the six MFMAs they replace.
+constexpr int CRT = 4;         // tail dates of the tail form (one per k-pair lane group)
+#ifndef PQ_GCAP_TAIL_P1
+#define PQ_GCAP_TAIL_P1 0      // 1: pass 1 of the tail form on fma() as well (A/B build)
+#endif
+template <int MGC, int NB, int TL = 0>
 __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_admm_gcap(pq_lowrank lr, pq_problem pb, pq_state st, pq_gcap gc,
                                                   pq_settings s, int iters_call, const double* pc, int64_t ldpc,
                                                   int r0, const double* cc, const int32_t* cg_nzr,
@@ -533,6 +557,13 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // (NB = 2 with the wide form fits the CU's 160 KiB of LDS with g_part indexed by the date
   // within its wave's column block: each wave only ever writes its own block's 16 dates)
   constexpr int MGG = WIDE ? CMGW : 8;
+  constexpr bool TAIL = TL > 0;
+  static_assert(!TAIL || NB == 2, "the tail form is a 32-date form");
+  constexpr bool TAIL1 = TAIL && PQ_GCAP_TAIL_P1 != 0;   // pass 1 with the tail dates on fma()
+  constexpr int NB1 = TAIL1 ? 1 : NB;         // MFMA column blocks of pass 1
+  constexpr int RT1 = TAIL1 ? CRT : 1;
+  constexpr int RT = TAIL ? CRT : 1;          // tail dates (arrays keep one slot)
+  constexpr int GP = TAIL ? CG_MAX + CRT : CG_MAX;   // g_part dates per wave
   constexpr int CTN = CT * NB, CNWN = CTN / 64, CHWN = CTN / 32;   // threads, waves, half-waves
   constexpr int CG = CG_MAX * NB;                                   // dates per group
   constexpr int CTP1N = (CP1_ROWS / 16 + CNWN - 1) / CNWN;          // pass-1 row tiles per wave
@@ -543,7 +574,7 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
   __shared__ double g_muv[CG], g_su[CG], g_dinv[CG], g_rn[CG], g_qmax[CG], g_coef[CG];
   __shared__ double g_y[CG * CH_MAX];   // y_b = H_b^-1 s_b of every date
   constexpr int NPART = 5;                    // per wave and date: 4 maxima, mu.V
-  __shared__ double g_part[CNWN * CG_MAX * NPART];   // (wave, date of its column block, slot)
+  __shared__ double g_part[CNWN * GP * NPART];   // (wave, date of its column block -- tail form: of the group --, slot)
   __shared__ double g_gm[CG * 3];
   // per (date, row); the rows' bounds and rho are shared by the group's dates
   __shared__ double g_zg[CG * MGG], g_yg[CG * MGG], g_cgv[CG * MGG], g_cgx[CG * MGG],
@@ -575,7 +606,7 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // a group beyond pass 1's rows (U + mg > CP1_ROWS) or the MFMA N cannot be solved here:
   // its dates fail loudly (status NON_CONVEX, found = False) instead of dropping rows
   // (uniform exit, before any barrier; GroupPlan never builds such a group)
-  if (kU > CP1_ROWS || U > CU_MAX || G > CG || kU > k_ld) {
+  if (kU > CP1_ROWS || U > CU_MAX || G > (TAIL ? CG_MAX + CRT : CG) || kU > k_ld) {
     for (int g = t; g < G; g += CTN) st.status[d0 + g] = PQ_NON_CONVEX;
     return;
   }
@@ -586,7 +617,13 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
   if (t == 0) s_rho = gc.grho[grp];
   __syncthreads();
   const double rho = s_rho;
-  const GConst gk = gconst(lr, pb, s, d0, rho);
+  GConst gk = gconst(lr, pb, s, d0, rho);
+  if constexpr (TAIL) {   // the group's constants are uniform: scalar registers (pass 2 has no VGPRs to spare)
+    gk.c = readlane_f64(gk.c, 0);
+    gk.sqc = readlane_f64(gk.sqc, 0);
+    gk.d = readlane_f64(gk.d, 0);
+    gk.rho = readlane_f64(gk.rho, 0);
+  }
   if (t < mg) s_sr[t] = sqrt(row_rho(pb.lg[t], pb.ug[t], rho, s));
   if (t < CG) {
     const int g = t;
@@ -722,42 +759,56 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
     {
       const int z0 = loop_zero();
       const int kq = l >> 4, m0 = (l & 15) + z0;
-      const double* Vp[NB];
-      double wsc1[NB];
+      const double* Vp[NB1];
+      double wsc1[NB1];
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
+      for (int nb = 0; nb < NB1; ++nb) {
         const int m = m0 + 16 * nb;
         Vp[nb] = (m < G) ? st.work + (int64_t)(d0 + m) * st.work_stride + ld : nullptr;
         wsc1[nb] = m < G ? g_dinv[m] : 1.0;
       }
-      f64x4 c[CTP1N][NB];
+      f64x4 c[CTP1N][NB1];
+      double ta[CTP1N][RT1];   // tail form: row l & 15 of tile j x tail date d, this lane's k pairs
       const double* arow[CTP1N];
       bool tv[CTP1N], aval[CTP1N];
       const int wu = __builtin_amdgcn_readfirstlane(w);   // (tv: wave-uniform, a scalar branch)
 #pragma unroll
       for (int j = 0; j < CTP1N; ++j) {
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) c[j][nb] = f64x4{0.0, 0.0, 0.0, 0.0};
+        for (int nb = 0; nb < NB1; ++nb) c[j][nb] = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int d = 0; d < RT1; ++d) ta[j][d] = 0.0;
         const int u = (w + CNWN * j) * 16 + m0;
         tv[j] = wu + CNWN * j < ntile;
         aval[j] = u < U + mg;
         arow[j] = u < U ? lr.panel + (int64_t)s_urow[u] * lr.ldp : pb.Cg + (int64_t)(u < U + mg ? u - U : 0) * ld;
       }
-      struct Buf { double2 b[NB]; double2 a[CTP1N]; double bs[NB]; };
+      struct Buf { double2 b[NB1]; double2 a[CTP1N]; double bs[NB1]; double2 t[RT1]; double ks; };
       // unconditional loads from clamped addresses, no select on a loaded register (see pass 2's
       // load): rows past U + mg and tiles past ntile produce output rows nobody reads, and the
       // columns past n meet a zero V (scaled by 0, after the load)
-      const double* Vq[NB];
+      const double* Vq[NB1];
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) Vq[nb] = Vp[nb] ? Vp[nb] : st.work + (int64_t)d0 * st.work_stride + ld;
+      for (int nb = 0; nb < NB1; ++nb) Vq[nb] = Vp[nb] ? Vp[nb] : st.work + (int64_t)d0 * st.work_stride + ld;
+      // tail dates: V of date 16 + d (wave-uniform pointers; dates past G read date 0's V, and
+      // their sums are dropped by a select when WU is written)
+      const double* Vt[RT1];
+#pragma unroll
+      for (int d = 0; d < RT1; ++d)
+        Vt[d] = st.work + (int64_t)(d0 + z0 + (TAIL1 && CG_MAX + d < G ? CG_MAX + d : 0)) * st.work_stride + ld;
       auto load = [&](Buf& f, int k0) {
         const int kk = k0 + 2 * kq;
         const bool kin = kk + 1 < n;
         const int kc = kin ? kk : 0;
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
+        for (int nb = 0; nb < NB1; ++nb) {
           f.b[nb] = *reinterpret_cast<const double2*>(Vq[nb] + kc);
           f.bs[nb] = (Vp[nb] && kin) ? 1.0 : 0.0;
+        }
+        if constexpr (TAIL1) {   // the 16 lanes of a k pair read the same 16 bytes
+#pragma unroll
+          for (int d = 0; d < RT1; ++d) f.t[d] = *reinterpret_cast<const double2*>(Vt[d] + kc);
+          f.ks = kin ? 1.0 : 0.0;
         }
 #pragma unroll
         for (int j = 0; j < CTP1N; ++j) f.a[j] = *reinterpret_cast<const double2*>(arow[j] + kc);
@@ -767,13 +818,25 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
       // unconditional, from clamped addresses)
       auto mma = [&](const Buf& f) {
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
+        for (int nb = 0; nb < NB1; ++nb) {
           const double bx = f.b[nb].x * f.bs[nb], by = f.b[nb].y * f.bs[nb];
 #pragma unroll
           for (int j = 0; j < CTP1N; ++j) {
             if (PQ_GCAP_SKIP1 && !tv[j]) continue;
             c[j][nb] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.a[j].x, bx, c[j][nb], 0, 0, 0);
             c[j][nb] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.a[j].y, by, c[j][nb], 0, 0, 0);
+          }
+        }
+        if constexpr (TAIL1) {   // the tail dates on the vector pipe, beside block 0's MFMAs
+#pragma unroll
+          for (int d = 0; d < RT1; ++d) {
+            const double tx = f.t[d].x * f.ks, ty = f.t[d].y * f.ks;
+#pragma unroll
+            for (int j = 0; j < CTP1N; ++j) {
+              if (PQ_GCAP_SKIP1 && !tv[j]) continue;
+              ta[j][d] = fma(f.a[j].x, tx, ta[j][d]);
+              ta[j][d] = fma(f.a[j].y, ty, ta[j][d]);
+            }
           }
         }
       };
@@ -791,7 +854,7 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
         const int tile = w + CNWN * j;
         if (tv[j]) {
 #pragma unroll
-          for (int nb = 0; nb < NB; ++nb) {
+          for (int nb = 0; nb < NB1; ++nb) {
             const int m = m0 + 16 * nb;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -803,6 +866,29 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 if (m < G) g_cgv[m * MGG + (u - U)] = cgv;
                 WU[u * CG + m] = s_sr[u - U] * cgv;
               }
+            }
+          }
+          if constexpr (TAIL1) {
+            // the four k-pair partials of row m0 in a fixed order ((l, l^16), (l^32, l^48): the
+            // same bits in all four lanes); lane group kq then writes tail date 16 + kq.
+            // Dates past G (and columns 16 + CRT .. 31, never written) stay zero
+            double tsel = 0.0;
+#pragma unroll
+            for (int d = 0; d < RT1; ++d) {
+              double x = ta[j][d];
+              x += __shfl_xor(x, 16, 64);
+              x += __shfl_xor(x, 32, 64);
+              tsel = kq == d ? x : tsel;
+            }
+            const int m = CG_MAX + kq, u = tile * 16 + m0;
+            const bool live = m < G;
+            const double wsc = live ? g_dinv[live ? m : 0] : 0.0;
+            if (u < U) {
+              WU[u * CG + m] = live ? gk.sqc * wsc * tsel : 0.0;
+            } else if (u < U + mg) {
+              const double cgv = wsc * tsel;
+              if (live) g_cgv[m * MGG + (u - U)] = cgv;
+              WU[u * CG + m] = live ? s_sr[u - U] * cgv : 0.0;
             }
           }
         }
@@ -1092,13 +1178,15 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
       const int z0 = loop_zero();
       const int kq = l >> 4, ia = (l & 15) + z0;
       const int Uk = (U + 3) & ~3;
-      const int cb = w / CNW, wb = w - cb * CNW;   // column block of this wave, wave within it
+      // (tail form: one MFMA column block, all CNWN waves walk asset blocks)
+      const int cb = TAIL ? 0 : w / CNW, wb = w - cb * CNW;   // column block of this wave, wave within it
+      constexpr int PSTEP = TAIL ? CNWN : CNW;
 #ifndef PQ_GCAP_PS
 #define PQ_GCAP_PS 4
 #endif
       constexpr int PS = PQ_GCAP_PS;   // union rows per pass-2 load step (x 4 lanes)
-      // the lane's dates: slot r -> date 16 cb + kq + 4 r
-      constexpr int NR = 4;
+      // the lane's dates: slot r -> date 16 cb + kq + 4 r; tail form: a fifth slot, date 16 + kq
+      constexpr int NR = TAIL ? 5 : 4;
       bool mact[NR];
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
@@ -1116,10 +1204,13 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
         for (int e = 0; e < 4; ++e) mv[r][e] = 0.0;
       }
-      for (int p = wb; p * 32 < n; p += CNW) {
+      for (int p = wb; p * 32 < n; p += PSTEP) {
         const int i = p * 32 + 2 * ia;   // this lane's asset pair (n even: i < n => i + 1 < n)
         const bool cin = i < n;
         f64x4 ce = f64x4{0.0, 0.0, 0.0, 0.0}, co = f64x4{0.0, 0.0, 0.0, 0.0};
+        double2 te[RT];   // tail form: Ut' X of tail date d for the asset pair, this lane's union rows
+#pragma unroll
+        for (int d = 0; d < RT; ++d) te[d] = double2{0.0, 0.0};
         struct ABuf { double2 a[PS]; };
         // unconditional loads from clamped addresses and no select on a loaded register: a
         // conditional load becomes an exec-masked block whose else-branch zeroes the load's
@@ -1141,6 +1232,18 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
             const double av = u < U ? UT[u * CG + 16 * cb + ia] : 0.0;   // Ut'[date 16 cb + ia][u]
             ce = __builtin_amdgcn_mfma_f64_16x16x4f64(av, f.a[h].x, ce, 0, 0, 0);
             co = __builtin_amdgcn_mfma_f64_16x16x4f64(av, f.a[h].y, co, 0, 0, 0);
+            if constexpr (TAIL) {   // Ut[u][16 .. 16 + CRT): one address per k group (LDS broadcast)
+              static_assert(CRT == 4, "two 16-byte LDS reads per union row");
+              const double2* tp = reinterpret_cast<const double2*>(UT + (u < U ? u : 0) * CG + CG_MAX);
+              const double2 t01 = tp[0], t23 = tp[1];
+              const double us = u < U ? 1.0 : 0.0;
+              const double tv4[4] = {t01.x * us, t01.y * us, t23.x * us, t23.y * us};
+#pragma unroll
+              for (int d = 0; d < RT; ++d) {
+                te[d].x = fma(tv4[d], f.a[h].x, te[d].x);
+                te[d].y = fma(tv4[d], f.a[h].y, te[d].y);
+              }
+            }
           }
         };
         ABuf f0, f1;
@@ -1151,7 +1254,25 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
           load(f0, u0 + 8 * PS);
           mma(f1, u0 + 4 * PS);
         }
+        // tail form: the four k groups' partials in a fixed order ((l, l^16), (l^32, l^48)); lane
+        // group kq keeps tail date 16 + kq as its fifth slot
+        double2 tsel = double2{0.0, 0.0};
+        if constexpr (TAIL) {
+#pragma unroll
+          for (int d = 0; d < RT; ++d) {
+            double x = te[d].x, y = te[d].y;
+            x += __shfl_xor(x, 16, 64);
+            y += __shfl_xor(y, 16, 64);
+            x += __shfl_xor(x, 32, 64);
+            y += __shfl_xor(y, 32, 64);
+            tsel = kq == d ? double2{x, y} : tsel;
+          }
+        }
         if (!cin) continue;
+        // tail form: the lane's date rows re-derived per asset block (loop_zero), so that the five
+        // slots' per-date offsets and LDS addresses are computed here instead of being hoisted
+        // above the asset-block loop and spilled (43 dwords; the other forms hoist 10)
+        const int kqe = TAIL ? kq + loop_zero() : kq;
         // per-asset data, shared by the lane's dates
         // register-resident columns: MGL of them (0 for the box-only and the wide forms; the
         // arrays keep one slot so they are never zero-length, but no loop reads past MGL --
@@ -1185,7 +1306,7 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
         for (int r = 0; r < NR; ++r) {
           __builtin_amdgcn_sched_barrier(0);   // one date's loads live at a time (VGPR budget)
           if (!mact[r]) continue;
-          const int m = 16 * cb + kq + 4 * r;
+          const int m = 16 * cb + kqe + 4 * r;
           const int bm = d0 + m;
           const double su = g_su[m], dinv = g_dinv[m];
           double2 lo = lo2, up = up2, rb = rb2;
@@ -1278,8 +1399,9 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
             mv[r][3] = fmax(mv[r][3], fmax(fabs(pxn), fabs(cy)));
             muv[r] = fma(mui, rr * dinv, muv[r]);
           };
-          one(ce[r], rr2.x, mu2.x, x2.x, px2.x, q2.x, z2.x, y2.x, lo.x, up.x, rb.x, 0, xo.x, pxo.x, zo.x, yo.x, ro.x);
-          one(co[r], rr2.y, mu2.y, x2.y, px2.y, q2.y, z2.y, y2.y, lo.y, up.y, rb.y, 1, xo.y, pxo.y, zo.y, yo.y, ro.y);
+          const double xre = r < 4 ? ce[r < 4 ? r : 0] : tsel.x, xro = r < 4 ? co[r < 4 ? r : 0] : tsel.y;
+          one(xre, rr2.x, mu2.x, x2.x, px2.x, q2.x, z2.x, y2.x, lo.x, up.x, rb.x, 0, xo.x, pxo.x, zo.x, yo.x, ro.x);
+          one(xro, rr2.y, mu2.y, x2.y, px2.y, q2.y, z2.y, y2.y, lo.y, up.y, rb.y, 1, xo.y, pxo.y, zo.y, yo.y, ro.y);
           *reinterpret_cast<double2*>(x_m) = xo;
           *reinterpret_cast<double2*>(Px_m) = pxo;
           *reinterpret_cast<double2*>(R_m) = ro;
@@ -1301,7 +1423,7 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
         }
         const int m = 16 * cb + kq + 4 * r;
         if (ia == 0) {
-          double* pp = g_part + (w * CG_MAX + (m - 16 * cb)) * NPART;
+          double* pp = g_part + (w * GP + (m - 16 * cb)) * NPART;
 #pragma unroll
           for (int e = 0; e < 4; ++e) pp[e] = mv[r][e];
           pp[4] = muv[r];
@@ -1316,8 +1438,10 @@ __global__ __launch_bounds__(CT * NB) __attribute__((amdgpu_waves_per_eu(2, 2)))
       // mv: |Cx-z| max(|Cx|,|z|) - |dres| max(|Px|,|C'y|) - |q| (the 7-slot form of admm_grp)
       double mv[7] = {g_gm[g * 3], fmax(g_gm[g * 3 + 1], g_gm[g * 3 + 2]), 0.0, 0.0, 0.0, 0.0, g_qmax[g]};
       double muv = 0.0;
-      for (int ww = (g / 16) * CNW; ww < (g / 16 + 1) * CNW; ++ww) {   // the waves of g's column block
-        const double* pp = g_part + (ww * CG_MAX + (g & 15)) * NPART;
+      // the waves of g's column block; tail form: all waves, (wave, date of the group)
+      const int ww0 = TAIL ? 0 : (g / 16) * CNW, ww1 = TAIL ? CNWN : (g / 16 + 1) * CNW;
+      for (int ww = ww0; ww < ww1; ++ww) {
+        const double* pp = g_part + (ww * GP + (TAIL ? g : (g & 15))) * NPART;
         mv[0] = fmax(mv[0], pp[0]);
         mv[1] = fmax(mv[1], pp[1]);
         mv[3] = fmax(mv[3], pp[2]);
@@ -1428,6 +1552,19 @@ static int gcap_check(const pq_lowrank* lr, const pq_problem* pb, const pq_gcap*
 // the plan has groups of more than 16 dates
 static int gcap_nb(const pq_gcap* gc) { return gc->gmax > pq::CG_MAX ? 2 : 1; }
 
+// The form of k_admm_gcap for a plan whose largest group has gmax dates and a problem with mg
+// general rows: 1 = the 16-date form, 2 = the 32-date form with both column blocks on the MFMA,
+// 3 = the tail form (16 < gmax <= 16 + CRT: dates 16 .. on the vector pipe; groups of such a
+// launch with 16 dates or fewer have no tail).  The wide form (mg > CMG) keeps both blocks on
+// the MFMA.  PQ_GCAP_TAIL = 0 forces form 2 (A/B); read on every call, so one process can run
+// both (a captured graph keeps the form it was captured with).
+extern "C" int pq_gcap_form(int32_t gmax, int32_t mg) {
+  if (gmax <= pq::CG_MAX) return 1;
+  if (gmax > pq::CG_MAX + pq::CRT || mg > pq::CMG) return 2;
+  const char* e = getenv("PQ_GCAP_TAIL");
+  return (e && atoi(e) == 0) ? 2 : 3;
+}
+
 extern "C" int pq_gcap_assemble(const pq_lowrank* lr, const pq_problem* pb, const pq_gcap* gc,
                                 const pq_settings* s, const double* band, int64_t ldo, int32_t r0,
                                 const double* pc, int64_t ldpc, const double* cc, void* stream) {
@@ -1495,7 +1632,19 @@ extern "C" int pq_admm_lr_gcap(const pq_lowrank* lr, const pq_problem* pb, pq_st
                pq::CNZ);
   const dim3 grid(gc->ngroups);
   const hipStream_t str = (hipStream_t)stream;
-  if (gcap_nb(gc) == 2) {   // 32-date groups (one 512-thread workgroup per group)
+  const int form = pq_gcap_form(gc->gmax, pb->mg);
+  if (form == 3) {   // 32-date workgroups, the dates past 16 (at most CRT) on the vector pipe
+    const dim3 blk(pq::CT * 2);
+    if (pb->mg == 0)
+      hipLaunchKernelGGL((pq::k_admm_gcap<0, 2, 1>), grid, blk, 0, str, *lr, *pb, *st, *gc, *s, iters_this_call, pc,
+                         ldpc, r0, cc, nullptr, nullptr, 0);
+    else if (pb->mg == 1)
+      hipLaunchKernelGGL((pq::k_admm_gcap<1, 2, 1>), grid, blk, 0, str, *lr, *pb, *st, *gc, *s, iters_this_call, pc,
+                         ldpc, r0, cc, nullptr, nullptr, 0);
+    else
+      hipLaunchKernelGGL((pq::k_admm_gcap<pq::CMG, 2, 1>), grid, blk, 0, str, *lr, *pb, *st, *gc, *s, iters_this_call,
+                         pc, ldpc, r0, cc, nullptr, nullptr, 0);
+  } else if (form == 2) {   // 32-date groups (one 512-thread workgroup per group)
     const dim3 blk(pq::CT * 2);
     if (pb->mg == 0)
       hipLaunchKernelGGL((pq::k_admm_gcap<0, 2>), grid, blk, 0, str, *lr, *pb, *st, *gc, *s, iters_this_call, pc, ldpc,
