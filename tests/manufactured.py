@@ -1,0 +1,397 @@
+"""Window-form QPs whose optimum and free set are known by construction (TEST INFRASTRUCTURE
+ONLY; plain numpy / scipy; of the package only the synthetic panel generator is imported).
+
+For a window (rows X of the float64 panel, the float64 window mean mu, or none) the objective
+matrix is, in np.longdouble and from the same float64 arrays the kernels are given,
+
+    P = psw (X - mu)'(X - mu) + p_diag I        (psw = p_scale w_scale)
+
+``manufacture`` takes a free set F, a point x* that is strictly inside the box on F, at a
+bound elsewhere and meets the shared rows lg <= C x <= ug, and the rows that are to be active.
+With s = max |P x*| it draws strictly complementary multipliers -- |z_i| in [0.5, 1.5] s on the
+variables at a bound, with the sign of the bound (z <= 0 at lb, >= 0 at ub: tests/kkt.py),
+lambda_r in [0.5, 1.5] s on the active inequality rows (upper side), a multiplier of size s on
+every equality row -- and sets
+
+    q = -(P x* + C' lambda + z)   rounded to float64.
+
+q is a per-problem input of the engine, so every date of a batch has its own F under a shared
+box and shared rows.  Rounding q moves the optimum of the float64 problem by ~cond(P_FF) u, so
+the reduced KKT system of (F, active rows) is then solved once more for the rounded q (LU in
+float64, five refinement steps on longdouble residuals): the returned x*, lambda, z are the
+optimum of exactly the inputs the kernels get, to longdouble rounding, and ``moved`` records
+how far that solve moved x* (relative).  x* is the unique optimum when the multipliers are
+strictly complementary and the reduced Hessian Z'P_FF Z is positive definite on the null space
+Z of the active rows' free columns: both margins are returned, and tests/test_manufactured.py
+asserts them.  Centred windows of T rows have rank T - 1, so without a ridge k <= T / 2 is
+used; beyond, a ridge of RIDGE[family] x mean diag P.
+
+``reduced_kkt_f64`` is the float64 yardstick of tests/test_polish_buckets_gpu.py: P_FF and the
+right-hand side formed in float64 from the float64 window, the regularised reduced KKT of
+polish.hip's header comment,
+
+    [P_FF + d I   C_aF'] [x_F]   [-q_F - P_FB x_B]
+    [C_aF        -d I  ] [lam] = [ d_a - C_aB x_B ]        d = Settings.delta x problem scale,
+
+solved with np.linalg.solve and at most ``refine`` proximal refinement steps started from a
+given point, ended by the kernels' own residual test (``stop``).  It restates the kernels'
+algebra, not their summation order: the yardstick in the same sense as
+admm_reference.admm_woodbury_f64 for the ADMM tests.
+
+``family`` builds the four families of batches (A: centred, box [0, 1], budget; B: centred, box
+[0, 0.05], weights at the upper bound; C: budget + 10 sector caps; W: uncentred, box [-1, 1])
+on consecutive daily windows of the synthetic factor panel.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+
+import numpy as np
+import scipy.linalg as sla
+
+from porqua_amd.synthetic import factor_panel
+
+LD = np.longdouble
+N, T = 300, 120
+# ridge = RIDGE[family] x mean diag P of the batch's ridged dates.  0.05 where only the parity bars apply (W);
+# the families whose dates meet the tight bar of tests/test_polish_buckets_gpu.py take the ridge at which
+# stop_rule_bound stays under 1e-10 for every date (tests/test_manufactured.py)
+RIDGE = {"A": 4.0, "B": 1.0, "C": 1.0, "W": 0.05}
+SEED = 20250711
+
+
+def window_P(X, mu, psw, p_diag):
+    """P in longdouble from the float64 window rows, mean and scalars."""
+    Xl = X.astype(LD) if mu is None else X.astype(LD) - np.asarray(mu).astype(LD)
+    P = LD(psw) * (Xl.T @ Xl)
+    P[np.diag_indices_from(P)] += LD(p_diag)
+    return P
+
+
+@dataclass
+class Optimum:
+    """One date: the float64 inputs q and p_diag, and the longdouble optimum."""
+    F: np.ndarray            # free set, ascending
+    side: np.ndarray         # (n) 0 free, 1 at lb, 2 at ub
+    act: np.ndarray          # (mg) bool: active rows (equalities included)
+    q: np.ndarray            # float64
+    p_diag: float
+    x: np.ndarray            # longdouble
+    lam: np.ndarray          # longdouble (mg), 0 on inactive rows
+    z: np.ndarray            # longdouble (n), 0 on F
+    s: float                 # max |P x*|
+    margins: dict = field(default_factory=dict)
+
+    @property
+    def k(self):
+        return len(self.F)
+
+
+def _solve_ld(M, rhs, steps=5):
+    """M sol = rhs with M, rhs longdouble: LU in float64, refinement on longdouble residuals."""
+    lu = sla.lu_factor(M.astype(np.float64))
+    sol = sla.lu_solve(lu, rhs.astype(np.float64)).astype(LD)
+    for _ in range(steps):
+        sol = sol + sla.lu_solve(lu, (rhs - M @ sol).astype(np.float64)).astype(LD)
+    return sol
+
+
+def manufacture(P, lb, ub, C, lg, ug, x0, side, act, rng, p_diag=0.0, norm_width=None) -> Optimum:
+    """See the module docstring.  ``P`` longdouble (ridge included), ``x0`` the chosen point,
+    ``side`` 0 / 1 / 2 per variable, ``act`` the rows to be active.  ``norm_width``: the margin
+    x*_F must keep from either bound (default 10 % of the box width)."""
+    n = len(x0)
+    C = np.asarray(C, dtype=np.float64).reshape(-1, n)
+    mg = C.shape[0]
+    eq = lg == ug
+    act = np.asarray(act, dtype=bool) | eq
+    F, B = np.flatnonzero(side == 0), np.flatnonzero(side != 0)
+    x = np.asarray(x0).astype(LD)
+    x[side == 1], x[side == 2] = lb[side == 1], ub[side == 2]
+    Cl = C.astype(LD)
+    s = float(np.abs(P @ x).max())
+    z = np.zeros(n, LD)
+    z[B] = np.where(side[B] == 1, -1.0, 1.0) * rng.uniform(0.5, 1.5, len(B)) * s
+    lam = np.zeros(mg, LD)
+    lam[act & ~eq] = rng.uniform(0.5, 1.5, int((act & ~eq).sum())) * s
+    lam[eq] = np.where(rng.uniform(size=int(eq.sum())) < 0.5, -1.0, 1.0) * s
+    q = (-(P @ x + Cl.T @ lam + z)).astype(np.float64)
+    # the optimum of the rounded inputs on the same (F, active rows)
+    k, ma = len(F), int(act.sum())
+    d_a = np.where(np.isfinite(ug), ug, lg)[act].astype(LD)
+    M = np.zeros((k + ma, k + ma), LD)
+    M[:k, :k] = P[np.ix_(F, F)]
+    M[:k, k:] = Cl[act][:, F].T
+    M[k:, :k] = Cl[act][:, F]
+    rhs = np.concatenate([-q[F].astype(LD) - P[np.ix_(F, B)] @ x[B], d_a - Cl[act][:, B] @ x[B]])
+    sol = _solve_ld(M, rhs)
+    moved = float(np.abs(sol[:k] - x[F]).max() / np.abs(x).max())
+    x[F] = sol[:k]
+    lam = np.zeros(mg, LD)
+    lam[act] = sol[k:]
+    g = P @ x + q.astype(LD) + Cl.T @ lam
+    z = np.zeros(n, LD)
+    z[B] = -g[B]
+    rr = np.abs(M @ sol - rhs)   # stationarity rows relative to s, the rows of C absolute (x* is O(1))
+    res = float(max(rr[:k].max() / max(s, 1e-300), rr[k:].max(initial=0.0)))
+    # margins
+    Pff = P[np.ix_(F, F)].astype(np.float64)
+    Z = sla.null_space(C[act][:, F]) if ma else np.eye(k)
+    ev = np.linalg.eigvalsh(Z.T @ Pff @ Z) if Z.shape[1] else np.array([np.inf])
+    zsign = np.where(side[B] == 1, -1.0, 1.0) * z[B]
+    cx = Cl @ x
+    slack = np.minimum(np.where(np.isfinite(ug), ug - cx, np.inf), np.where(np.isfinite(lg), cx - lg, np.inf))
+    width = (ub - lb)[F]
+    margins = dict(
+        lam_min=float(ev.min()), lam_min_rel=float(ev.min() / np.mean(np.diag(Pff))),
+        cond=float(np.linalg.cond(Pff)), z_min_rel=float(zsign.min() / s) if len(B) else np.inf,
+        row_min_rel=float(lam[act & ~eq].min() / s) if (act & ~eq).any() else np.inf,
+        slack_min=float(slack[~act].min()) if (~act).any() else np.inf,
+        gap=float(np.minimum(x[F] - lb[F], ub[F] - x[F]).min()),
+        gap_need=float(norm_width if norm_width is not None else 0.1 * width.min()),
+        moved=moved, kkt_res=res)
+    return Optimum(F=F, side=side.copy(), act=act, q=q, p_diag=float(p_diag), x=x, lam=lam, z=z, s=s,
+                   margins=margins)
+
+
+def problem_scale(X, mu, psw, p_diag, q):
+    """The kernels' problem scale (k_pg_init): max(|q|inf, max_i |psw dg_i + p_diag|), dg the window's
+    sums of squares."""
+    Xc = X if mu is None else X - mu
+    return max(float(np.abs(q).max()), float(np.abs(psw * (Xc * Xc).sum(0) + p_diag).max()), 1e-300)
+
+
+STOP_REL = 1e-13      # the polish kernels end the refinement at a residual of STOP_REL x problem scale ...
+ROW_ZERO = 1e-14      # ... with a row residual within ROW_ZERO (1 + |d_a| + |C_aF x_F|) taken as zero
+
+
+def reduced_kkt_f64(X, mu, psw, p_diag, q, C, lg, ug, lb, ub, side, act, x0, lam0, delta, refine, stop=None):
+    """The float64 yardstick (module docstring): returns (x, lam, z_box, steps), of length n / mg / n.
+    ``side`` 0 / 1 / 2 per variable, ``act`` bool per row, (x0, lam0) the starting point
+    (the ADMM point), ``delta`` absolute.  ``stop`` (absolute; None: every step is taken): the
+    stop rule every polish kernel applies before a step (polish.hip, polish_w.hip, k_pg_solve,
+    k_pg_big, rt_solve_date alike) -- the refinement ends once max(|r_F|, |r_a|) <= stop, a row
+    residual r_a within ROW_ZERO (1 + |d_a| + |C_aF x_F|) counting as zero.  It is part of the
+    kernels' algorithm, not of their summation order: without it the model refines on to
+    cond(P_FF) u where the kernels, by design, stop at ~ stop / lambda_min(P_FF)."""
+    n = len(q)
+    C = np.asarray(C, dtype=np.float64).reshape(-1, n)
+    Xc = X if mu is None else X - mu
+    F, B = np.flatnonzero(side == 0), np.flatnonzero(side != 0)
+    k, ma = len(F), int(np.sum(act))
+    xb = np.where(side == 1, lb, np.where(side == 2, ub, 0.0))
+    Xf = Xc[:, F]
+    Pff = psw * (Xf.T @ Xf) + p_diag * np.eye(k)
+    rF = -q[F] - psw * (Xf.T @ (Xc[:, B] @ xb[B]))
+    Ca = C[act]
+    dA = np.where(np.isfinite(ug), ug, lg)[act] - Ca[:, B] @ xb[B]
+    M = np.zeros((k + ma, k + ma))
+    M[:k, :k] = Pff
+    M[:k, k:] = Ca[:, F].T
+    M[k:, :k] = Ca[:, F]
+    Mreg = M.copy()
+    Mreg[:k, :k] += delta * np.eye(k)
+    Mreg[k:, k:] -= delta * np.eye(ma)
+    rhs = np.concatenate([rF, dA])
+    sol = np.concatenate([x0[F], lam0[act]])
+    steps = 0
+    for _ in range(refine):
+        r = rhs - M @ sol
+        if ma:
+            ra = r[k:]
+            ra[np.abs(ra) <= ROW_ZERO * (1.0 + np.abs(dA) + np.abs(Ca[:, F] @ sol[:k]))] = 0.0
+        if stop is not None and np.abs(r).max() <= stop:
+            break
+        sol = sol + np.linalg.solve(Mreg, r)
+        steps += 1
+    x = xb.copy()
+    x[F] = sol[:k]
+    lam = np.zeros(C.shape[0])
+    lam[act] = sol[k:]
+    g = psw * (Xc.T @ (Xc @ x)) + p_diag * x + q + C.T @ lam
+    zb = np.where(side != 0, -g, 0.0)
+    return x, lam, zb, steps
+
+
+def stop_rule_bound(P, q, C, lg, ug, o: Optimum, sc):
+    """The largest distance from (x*, lambda, z) of ANY point the kernels' stop rule admits, relative as
+    in the tight bar: with the residual r of the reduced KKT system bounded by |r_F| <= STOP_REL sc and
+    |r_a| <= max(STOP_REL sc, ROW_ZERO (1 + 2 |d_a|)), the error is M^-1 r, so |e| <= |M^-1| r_max
+    entrywise, and that of z_B likewise through [P_BF C_aB'] M^-1 (float64 inverse of the unregularised M; P float64 n x n).  Returns (bound on
+    |x - x*|inf / |x*|inf, bound on the multipliers' distance / s).  A date whose bound is under
+    1e-10 meets 10 d_model <= 1e-9 from whatever ADMM point the refinement starts."""
+    F, B = o.F, np.flatnonzero(o.side != 0)
+    k, Ca = len(F), C[o.act]
+    ma = Ca.shape[0]
+    M = np.zeros((k + ma, k + ma))
+    M[:k, :k] = P[np.ix_(F, F)]
+    M[:k, k:] = Ca[:, F].T
+    M[k:, :k] = Ca[:, F]
+    dA = np.abs(np.where(np.isfinite(ug), ug, lg)[o.act])
+    rmax = np.concatenate([np.full(k, STOP_REL * sc), np.maximum(STOP_REL * sc, ROW_ZERO * (1.0 + 2.0 * dA))])
+    Mi = np.linalg.inv(M)
+    e = np.abs(Mi) @ rmax
+    # z_B = -(P x + q + C' lambda)_B: its error is [P_BF  C_aB'] M^-1 r
+    ez = np.abs(np.hstack([P[np.ix_(B, F)], Ca[:, B].T]) @ Mi) @ rmax if len(B) else np.zeros(1)
+    return float(e[:k].max() / np.abs(o.x).max()), float(max(e[k:].max(initial=0.0), ez.max()) / o.s)
+
+
+# ----------------------------------------------------------------------------------------
+# the four families
+# ----------------------------------------------------------------------------------------
+
+A_SIZES = (2, 15, 16, 17, 47, 48, 49, 63, 64, 65, 79, 80, 81, 95, 96, 97, 127, 128, 129, 200, 255, 256, 257, 299)
+B_SIZES = (30, 48, 49, 64, 96, 97, 128, 200)
+C_SIZES = (40, 64, 90, 120)
+C_ACTIVE = (1, 7, 8)          # active sector caps of the three C batches: ma = 2, 8, 9
+W_FIXED = (0, 3, 7, 8)        # variables at a bound of the W dates: bordered rows 1, 4, 8, 9
+A_RIDGE_FROM = 63             # family A: no ridge up to k = 49
+NO_RIDGE_MAX = T // 2         # centred windows of rank T - 1
+
+
+def family_sizes(fam):
+    """The free-set size of every date.  Every size appears twice.  Dates without a ridge come first
+    (their group-capacitance groups are cut from the ridged ones: one capacitance serves dates of one
+    p_diag), then the ridged sizes in order, twice over, so that the groups see mixed free lists."""
+    if fam == "A":
+        lo = [k for k in A_SIZES if k < A_RIDGE_FROM]
+        hi = [k for k in A_SIZES if k >= A_RIDGE_FROM]
+    elif fam == "B":
+        lo = [k for k in B_SIZES if k <= NO_RIDGE_MAX]
+        hi = [k for k in B_SIZES if k > NO_RIDGE_MAX]
+    elif fam.startswith("C"):
+        lo = [k for k in C_SIZES if k <= NO_RIDGE_MAX]
+        hi = [k for k in C_SIZES if k > NO_RIDGE_MAX]
+    else:
+        lo, hi = [], [N - f for f in W_FIXED]
+    return np.array(lo + lo + hi + hi), 2 * len(lo)
+
+
+@dataclass
+class Batch:
+    fam: str
+    n: int
+    rows: np.ndarray          # (D, T) panel rows of every window
+    tlen: np.ndarray
+    R: np.ndarray             # the panel
+    centred: bool
+    p_scale: float
+    lb: np.ndarray
+    ub: np.ndarray
+    C: np.ndarray
+    lg: np.ndarray
+    ug: np.ndarray
+    sizes: np.ndarray
+    nplain: int               # the first nplain dates have no ridge
+    ridge: float = 0.0
+    opt: list = field(default_factory=list)
+
+    @property
+    def D(self):
+        return len(self.sizes)
+
+    @property
+    def breaks(self):
+        """GroupPlan breaks: a new group where the ridge starts."""
+        b = np.zeros(self.D, dtype=bool)
+        if 0 < self.nplain < self.D:
+            b[self.nplain] = True
+        return b
+
+    def psw(self, d):
+        return self.p_scale / (self.tlen[d] - 1.0) if self.centred else self.p_scale
+
+    def X(self, d):
+        return self.R[self.rows[d, :self.tlen[d]]]
+
+
+def family_windows(fam, n=N, t=T):
+    """The batch without its optima: panel, windows, box and rows (everything but q and p_diag)."""
+    sizes, nplain = family_sizes(fam)
+    D = len(sizes)
+    ends = np.arange(t + 5, t + 5 + D)
+    _, R, _, sec = factor_panel(int(ends.max()) + 1, n, n_sectors=10)
+    rows = (ends[:, None] - t + 1 + np.arange(t)[None, :]).astype(np.int32)
+    tlen = np.full(D, t, dtype=np.int32)
+    lb, ub = np.zeros(n), np.ones(n)
+    C, lg, ug = np.ones((1, n)), np.ones(1), np.ones(1)
+    if fam == "B":
+        ub = np.full(n, 0.05)
+    elif fam == "W":
+        lb = np.full(n, -1.0)
+    elif fam.startswith("C"):
+        C = np.vstack([C] + [(sec == g).astype(float)[None, :] for g in range(10)])
+    b = Batch(fam=fam, n=n, rows=rows, tlen=tlen, R=R, centred=fam != "W", p_scale=2.0, lb=lb, ub=ub, C=C,
+              lg=lg, ug=ug, sizes=sizes, nplain=nplain)
+    b.sec = sec
+    return b
+
+
+def family(fam, mu=None, seed=SEED) -> Batch:
+    """The batch of a family with its optima.  ``mu`` (D, n): the float64 window means the kernels
+    are given (read back from the device); default: numpy's means of the same windows."""
+    b = family_windows(fam)
+    n, D = b.n, b.D
+    rng = np.random.default_rng([seed, sum(map(ord, fam))])
+    if b.centred and mu is None:
+        mu = np.stack([b.X(d).mean(0) for d in range(D)])
+    b.mu = mu if b.centred else None
+    # one ridge for the batch (a group capacitance serves dates of one p_diag)
+    if b.nplain < D:
+        md = [float(np.mean(np.diag(window_P(b.X(d), None if b.mu is None else b.mu[d], b.psw(d), 0.0))))
+              for d in range(b.nplain, D)]
+        b.ridge = float(RIDGE[fam[0]] * np.mean(md))
+    if fam.startswith("C"):
+        nact = int(fam[1:])
+        tot = rng.uniform(0.9, 1.1, 10)
+        tot = tot / tot.sum()
+        tot[9] = 1.0 - tot[:9].sum()
+        active = np.zeros(10, dtype=bool)
+        active[rng.permutation(10)[:nact]] = True
+        b.lg = np.concatenate([[1.0], np.full(10, -np.inf)])
+        b.ug = np.concatenate([[1.0], np.where(active, tot, tot + 0.05)])
+        b.active = active
+    for d in range(D):
+        k = int(b.sizes[d])
+        pd = 0.0 if d < b.nplain else b.ridge
+        P = window_P(b.X(d), None if b.mu is None else b.mu[d], b.psw(d), pd)
+        side = np.ones(n, dtype=np.int64)
+        x0 = np.zeros(n)
+        act = np.zeros(b.C.shape[0], dtype=bool)
+        if fam.startswith("C"):
+            # the free variables dealt evenly over the sectors (a sector's total is shared by every date, so
+            # its free weights scale with 1 / their number); x*_F normalised per sector
+            F = np.sort(np.concatenate([rng.permutation(np.flatnonzero(b.sec == g))[:k // 10 + (g < k % 10)]
+                                        for g in range(10)]))
+            assert len(F) == k
+            side[F] = 0
+            r = rng.uniform(0.5, 1.5, n)
+            for g in range(10):
+                m = (b.sec == g) & (side == 0)
+                x0[m] = r[m] / r[m].sum() * b.ug[1 + g] if b.active[g] else r[m] / r[m].sum() * (b.ug[1 + g] - 0.05)
+            act[1:] = b.active
+        else:
+            F = np.sort(rng.permutation(n)[:k])
+            side[F] = 0
+            Bv = np.flatnonzero(side != 0)
+            if fam == "B":      # weights at the upper bound: mean x*_F nearest ub / 2, at least 2 of them
+                nup = int(np.clip(round((1.0 - k * 0.025) / 0.05), 2, len(Bv)))
+                side[rng.permutation(Bv)[:nup]] = 2
+            elif fam == "W":    # fixed variables at either bound
+                side[Bv] = 1 + (rng.uniform(size=len(Bv)) < 0.5)
+            xB = np.where(side == 1, b.lb, np.where(side == 2, b.ub, 0.0)).sum()
+            r = rng.uniform(0.5, 1.5, k)
+            x0[F] = r / r.sum() * (1.0 - xB)
+        norm_width = 1.0 / (4 * k)
+        b.opt.append(manufacture(P, b.lb, b.ub, b.C, b.lg, b.ug, x0, side, act, rng, p_diag=pd,
+                                 norm_width=norm_width))
+    return b
+
+
+FAMILIES = ("A", "B", "C1", "C7", "C8", "W")
+
+
+def in_tight_bar(fam, o: Optimum) -> bool:
+    """The date's last round runs on a solver reduced_kkt_f64 models (register tile, LDS solve, k_pg_big:
+    k <= PG_KBIG = 256 free variables and at most 8 active rows; family W takes the wide rounds)."""
+    return fam != "W" and o.k <= 256 and int(o.act.sum()) <= 8
