@@ -104,23 +104,13 @@ __global__ __launch_bounds__(PT) void k_polish(pq_problem pb, pq_state st, const
   // ---- classification from the ADMM point -------------------------------------------
   for (int i = t; i < ld; i += PT) {
     int f = 0;
-    if (i < n && has_box) {
-      const double zi = sz[st.mg_pad + i], yi = sy[st.mg_pad + i];
-      if (!isinf(lb[i]) && zi - lb[i] < -yi) f = 1;
-      else if (!isinf(ub[i]) && ub[i] - zi < yi) f = 2;
-      if (lb[i] == ub[i]) f = 1;
-    }
+    if (i < n && has_box) f = start_box(sz[st.mg_pad + i], sy[st.mg_pad + i], sx[i], lb[i], ub[i], -INFINITY);
     fl[i] = (i < n) ? f : 1;  // padding never free
     xs[i] = (i < n) ? sx[i] : 0.0;
   }
   if (t < mg) {
-    const double zr = sz[t], yr = sy[t];
-    int a = 0;
-    if (lg[t] == ug[t]) a = 2;
-    else if (!isinf(lg[t]) && zr - lg[t] < -yr) a = 1;
-    else if (!isinf(ug[t]) && ug[t] - zr < yr) a = 2;
-    act[t] = a;
-    lamF[t] = yr;   // multipliers start at the ADMM duals
+    act[t] = start_row(sz[t], sy[t], lg[t], ug[t]);
+    lamF[t] = sy[t];   // multipliers start at the ADMM duals
   }
   __syncthreads();
   PQ_STAMP(0);
@@ -253,18 +243,14 @@ __global__ __launch_bounds__(PT) void k_polish(pq_problem pb, pq_state st, const
         double sum = 0.0;
         for (int p = l; p < k; p += 64) sum += c[Fl[p]] * solx[p];
         sum = wave_sum(sum);
-        if (l == 0) {
-          const double v = dA[a] - sum;
-          // rounding-level residuals of a row with no free support must not move lam
-          rl[a] = fabs(v) <= 1e-14 * (1.0 + fabs(dA[a]) + fabs(sum)) ? 0.0 : v;
-        }
+        if (l == 0) rl[a] = row_residual(dA[a], sum);
       }
       __syncthreads();
-      {  // converged to rounding level: further refinement steps change nothing
+      {
         double rm = 0.0;
         for (int p = t; p < k; p += PT) rm = fmax(rm, fabs(rx[p]));
         if (t < ma) rm = fmax(rm, fabs(rl[t]));
-        if (block_max(rm, red) <= 1e-13 * sc) break;
+        if (refine_done(block_max(rm, red), sc)) break;
       }
       fwd_solve(K, ld, Dt, nbk, rx, t1, t64, y64p);
       // wl = U' t1 - rl ; dlam = S^-1 wl (S = Ls Ls', tiny, one thread)
@@ -275,18 +261,7 @@ __global__ __launch_bounds__(PT) void k_polish(pq_problem pb, pq_state st, const
         if (l == 0) wl[a] = sum - rl[a];
       }
       __syncthreads();
-      if (t == 0) {
-        for (int i = 0; i < ma; ++i) {            // forward Ls
-          double v = wl[i];
-          for (int j = 0; j < i; ++j) v -= stg[i * DP + j] * wl[j];
-          wl[i] = v / stg[i * DP + i];
-        }
-        for (int i = ma - 1; i >= 0; --i) {       // backward Ls'
-          double v = wl[i];
-          for (int j = i + 1; j < ma; ++j) v -= stg[j * DP + i] * wl[j];
-          wl[i] = v / stg[i * DP + i];
-        }
-      }
+      if (t == 0) schur_solve(stg, DP, ma, wl);
       __syncthreads();
       // t1 <- t1 - U dlam ; dx = L^-T t1
       for (int p = t; p < nbk * TB; p += PT) {
@@ -318,10 +293,9 @@ __global__ __launch_bounds__(PT) void k_polish(pq_problem pb, pq_state st, const
       const int f = fl[i];
       const double xi = xs[i];
       if (f == 0 && has_box) {
-        if (!isinf(lb[i]) && xi < lb[i] - ptol * (1.0 + fabs(lb[i]))) { fl[i] = 1; bad = 1; }
-        else if (!isinf(ub[i]) && xi > ub[i] + ptol * (1.0 + fabs(ub[i]))) { fl[i] = 2; bad = 1; }
-      } else if (f == 1 && lb[i] != ub[i] && -g[i] > dtol) { fl[i] = 0; bad = 1; }
-      else if (f == 2 && -g[i] < -dtol) { fl[i] = 0; bad = 1; }
+        const int c = box_cross(xi, lb[i], ub[i], ptol);
+        if (c) { fl[i] = c; bad = 1; }
+      } else if (f != 0 && bound_release(f, lb[i], ub[i], g[i], dtol)) { fl[i] = 0; bad = 1; }
     }
     for (int r = w; r < mg; r += PW) {
       const double* c = Cg + (int64_t)r * ld;
@@ -329,12 +303,8 @@ __global__ __launch_bounds__(PT) void k_polish(pq_problem pb, pq_state st, const
       for (int j = l; j < n; j += 64) sum += c[j] * xs[j];
       sum = wave_sum(sum);
       if (l == 0 && lg[r] != ug[r]) {
-        const int a = act[r];
-        const double lam = lamF[r];
-        if (a == 0 && sum > ug[r] + ptol * (1.0 + fabs(ug[r]))) { act[r] = 2; bad = 1; }
-        else if (a == 0 && sum < lg[r] - ptol * (1.0 + fabs(lg[r]))) { act[r] = 1; bad = 1; }
-        else if (a == 2 && lam < -dtol) { act[r] = 0; bad = 1; }
-        else if (a == 1 && lam > dtol) { act[r] = 0; bad = 1; }
+        const int a = row_verdict(act[r], sum, lg[r], ug[r], lamF[r], ptol, dtol);
+        if (a != act[r]) { act[r] = a; bad = 1; }
       } else if (l == 0 && fabs(sum - ug[r]) > 1e-10 * (1.0 + fabs(ug[r]))) {
         bad = 1;   // an equality row the reduced system could not satisfy (no free support)
       }

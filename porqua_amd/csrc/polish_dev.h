@@ -1,6 +1,7 @@
 // Device helpers of the K4 polish kernels (polish.hip: dense P; polish_w.hip: window form).
 #pragma once
 #include "chol_dev.h"
+#include "polish_rules.h"
 #include "../../include/porqua_hip.h"
 
 namespace pq {
@@ -8,22 +9,24 @@ namespace pq {
 constexpr int PT = 256;
 constexpr int PW = PT / 64;
 
-// Optional phase timing (build with -DPQ_PROFILE): wall-clock ticks per phase accumulated
-// into the 16 doubles after the work layout of each problem (tools/prof_polish.py).
+// Optional phase timing (build with -DPQ_PROFILE): wall-clock ticks per phase, since the last
+// stamp (the kernel keeps `long long t_last_ = wall_clock64()`), accumulated into R[slot].
+// PG_STAMP: the grouped per-date solvers, into the date's record; PQ_STAMP: the per-date
+// kernels, into the 16 doubles after the work layout of each problem (tools/prof_polish.py).
 #ifdef PQ_PROFILE
-#define PQ_STAMP(k)                                              \
+#define PG_STAMP(R, slot)                                        \
   do {                                                           \
     __syncthreads();                                             \
     if (threadIdx.x == 0) {                                      \
       const long long now_ = wall_clock64();                     \
-      prof[k] += (double)(now_ - t_last_);                       \
+      (R)[slot] += (double)(now_ - t_last_);                     \
       t_last_ = now_;                                            \
     }                                                            \
   } while (0)
 #else
-#define PQ_STAMP(k) do { } while (0)
+#define PG_STAMP(R, slot) do { } while (0)
 #endif
-
+#define PQ_STAMP(k) PG_STAMP(prof, k)
 
 // ---- the compact P_FF storage of the window-form polish (polish_w.hip, and the large free
 //      sets of the grouped pipeline, polish_g.hip): diagonal 64x64 tiles of P_FF in full,

@@ -18,12 +18,12 @@
 //   pass 1  (one workgroup per GROUP)  exact P x and gradient of the new point through the
 //                                       window (MFMA over the union), the active-set checks,
 //                                       and for accepted dates the final scoring.
-// The arithmetic of every step is polish_w.hip's (same classification, same regularised
-// reduced KKT, same refinement, same acceptance tests), so results agree with it to
-// rounding.  Dates the pipeline does not take (free set outside 1..128, more than 32
-// active rows, a failed factorisation, not accepted within polish_rounds) are marked
-// FALLBACK and left untouched for pq_polish_w_batched, which restarts them from the ADMM
-// point.
+// Classification, refinement stop and acceptance tests are the rules of polish_rules.h, which
+// polish_w.hip applies to the same regularised reduced KKT, so results agree with it to
+// rounding; the steps the per-date solvers here share are in pg_solve_dev.h.  Dates the
+// pipeline does not take (free set outside 1..128, more than 32 active rows, a failed
+// factorisation, not accepted within polish_rounds) are marked FALLBACK and left untouched
+// for pq_polish_w_batched, which restarts them from the ADMM point.
 //
 // Replaces, with polish_w.hip, the accuracy of qpsolvers' interior-point answer
 // (src/qp_problems.py:211-214); scoring as src/qp_problems.py:219-221 and
@@ -31,15 +31,14 @@
 #include <cstdlib>
 #include <mutex>
 
-#include "polish_dev.h"
+#include "pg_solve_dev.h"
 #include "capi_util.h"
-#include "pg_record.h"
 
 namespace pq {
 
 
 // ---------------------------------------------------------------------------------------
-// init: classification from the ADMM point (polish_w.hip's, verbatim) + problem scale
+// init: classification from the ADMM point (polish_rules.h) + problem scale
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(PT) void k_pg_init(pq_lowrank lr, pq_problem pb, pq_state st, double* rec,
                                                 pq_settings s) {
@@ -85,12 +84,7 @@ __global__ __launch_bounds__(PT) void k_pg_init(pq_lowrank lr, pq_problem pb, pq
   double nfree = 0.0;
   for (int i = t; i < ld; i += PT) {
     int f = 0;
-    if (i < n && has_box) {
-      const double zi = sz[st.mg_pad + i], yi = sy[st.mg_pad + i];
-      if (!isinf(lb[i]) && (zi - lb[i] < -yi || sx[i] - lb[i] < fix_thr)) f = 1;
-      else if (!isinf(ub[i]) && ub[i] - zi < yi) f = 2;
-      if (lb[i] == ub[i]) f = 1;
-    }
+    if (i < n && has_box) f = start_box(sz[st.mg_pad + i], sy[st.mg_pad + i], sx[i], lb[i], ub[i], fix_thr);
     wk.fl[i] = (i < n) ? f : 1;
     wk.xs[i] = (i < n) ? sx[i] : 0.0;
     nfree += (i < n && f == 0) ? 1.0 : 0.0;
@@ -100,11 +94,8 @@ __global__ __launch_bounds__(PT) void k_pg_init(pq_lowrank lr, pq_problem pb, pq
     int a = 0;
     double lam = 0.0;
     if (t < mg) {
-      const double zr = sz[t], yr = sy[t];
-      if (lg[t] == ug[t]) a = 2;
-      else if (!isinf(lg[t]) && zr - lg[t] < -yr) a = 1;
-      else if (!isinf(ug[t]) && ug[t] - zr < yr) a = 2;
-      lam = yr;
+      a = start_row(sz[t], sy[t], lg[t], ug[t]);
+      lam = sy[t];
     }
     R[R_ACT + t] = a;
     R[R_LAM + t] = lam;
@@ -1218,14 +1209,7 @@ __device__ __forceinline__ void pg_solve_date(int b, const pq_problem& pb, const
   const double delta = s.delta * sc;
   const double* K = st.K + (int64_t)b * st.K_stride;   // P_FF (both triangles), kept for the residuals
 #ifdef PQ_PROFILE
-  long long t_last_ = wall_clock64();
-#define WSTAMP(k_)                                                         \
-  do {                                                                     \
-    __syncthreads();                                                       \
-    if (t == 0) { const long long n_ = wall_clock64(); R[8 + (k_)] += (double)(n_ - t_last_); t_last_ = n_; } \
-  } while (0)
-#else
-#define WSTAMP(k_) do { } while (0)
+  long long t_last_ = wall_clock64();   // (PG_STAMP slots 8..13)
 #endif
   // the K scratch rows / columns of this round's free positions: identity, or (P_FF reused
   // from an earlier round's form) the positions in that free list
@@ -1273,13 +1257,13 @@ __device__ __forceinline__ void pg_solve_date(int b, const pq_problem& pb, const
       }
     }
   }
-  WSTAMP(0);
+  PG_STAMP(R, 8);
   __syncthreads();
   if (b_potrf<NW>(Lp, k, &s_flag, R + 16)) {
     if (t == 0) R[R_STATE] = PQ_PG_FALLBACK;
     return;
   }
-  WSTAMP(1);
+  PG_STAMP(R, 9);
   // U = L^-1 C_aF' (row a of the global U scratch), S = U'U + delta I
   for (int a = 0; a < ma; ++a) {
     const double* cr = Cg + (int64_t)s_al[a] * ld;
@@ -1289,40 +1273,16 @@ __device__ __forceinline__ void pg_solve_date(int b, const pq_problem& pb, const
     for (int p = t; p < k; p += T) wk.U[(int64_t)a * ld + p] = t2[p];
   }
   __syncthreads();
-  for (int e = w; e < ma * ma; e += NW) {
-    const int ii = e / ma, jj = e % ma;
-    if (jj > ii) continue;
-    const double* ui = wk.U + (int64_t)ii * ld;
-    const double* uj = wk.U + (int64_t)jj * ld;
-    double sum = 0.0;
-    for (int p = l; p < k; p += 64) sum += ui[p] * uj[p];
-    sum = wave_sum(sum);
-    if (l == 0) Sm[ii * WMA + jj] = sum + (ii == jj ? delta : 0.0);
-  }
+  pg_schur<T>(t, wk.U, ld, k, ma, delta, Sm, WMA);
   __syncthreads();
-  if (t == 0) {   // tiny Cholesky of S (ma <= 8), one lane
-    int sbad = 0;
-    for (int c = 0; c < ma && !sbad; ++c) {
-      double d = Sm[c * WMA + c];
-      for (int m = 0; m < c; ++m) d -= Sm[c * WMA + m] * Sm[c * WMA + m];
-      if (!(d > 0.0) || !isfinite(d)) { sbad = 1; break; }
-      d = sqrt(d);
-      Sm[c * WMA + c] = d;
-      for (int r = c + 1; r < ma; ++r) {
-        double v = Sm[r * WMA + c];
-        for (int m = 0; m < c; ++m) v -= Sm[r * WMA + m] * Sm[c * WMA + m];
-        Sm[r * WMA + c] = v / d;
-      }
-    }
-    s_flag = sbad;
-  }
+  if (t == 0) s_flag = schur_potrf(Sm, WMA, ma);
   __syncthreads();
   if (s_flag) {
     if (t == 0) R[R_STATE] = PQ_PG_FALLBACK;
     return;
   }
-  WSTAMP(2);
-  // ---- proximal iterative refinement (polish_w.hip, compact mode) ------------------------
+  PG_STAMP(R, 10);
+  // ---- proximal iterative refinement (the rules of polish_rules.h) -------------------------
   const int qs = (k + NW - 1) / NW, qa = w * qs, qb = min(k, qa + qs);
   for (int itr = 0; itr < s.refine_iters; ++itr) {
     // rx = rF - P_FF x - C_aF' lam: wave w sums the column slice [qa, qb) of P_FF x (P_FF
@@ -1339,10 +1299,7 @@ __device__ __forceinline__ void pg_solve_date(int b, const pq_problem& pb, const
       double sum = 0.0;
       for (int p = l; p < k; p += 64) sum += cr[wk.Fl[p]] * xF[p];
       sum = wave_sum(sum);
-      if (l == 0) {
-        const double v = dAv[a] - sum;
-        rl[a] = fabs(v) <= 1e-14 * (1.0 + fabs(dAv[a]) + fabs(sum)) ? 0.0 : v;
-      }
+      if (l == 0) rl[a] = row_residual(dAv[a], sum);
     }
     __syncthreads();
     double rm = 0.0;
@@ -1357,8 +1314,8 @@ __device__ __forceinline__ void pg_solve_date(int b, const pq_problem& pb, const
       rm = fmax(rm, fabs(v));
     }
     if (t < ma) rm = fmax(rm, fabs(rl[t]));
-    WSTAMP(3);
-    if (block_max(rm, red) <= 1e-13 * sc) break;   // (its barriers also order rx / sc4)
+    PG_STAMP(R, 11);
+    if (refine_done(block_max(rm, red), sc)) break;   // (its barriers also order rx / sc4)
     b_fwd<NW>(Lp, k, rx, t2);   // t2 = L^-1 rx (rx consumed)
     for (int a = w; a < ma; a += NW) {   // wl = U' t2 - rl
       const double* ua = wk.U + (int64_t)a * ld;
@@ -1368,18 +1325,7 @@ __device__ __forceinline__ void pg_solve_date(int b, const pq_problem& pb, const
       if (l == 0) wl[a] = sum - rl[a];
     }
     __syncthreads();
-    if (t == 0) {   // dlam = S^-1 wl
-      for (int ii = 0; ii < ma; ++ii) {
-        double v = wl[ii];
-        for (int jj = 0; jj < ii; ++jj) v -= Sm[ii * WMA + jj] * wl[jj];
-        wl[ii] = v / Sm[ii * WMA + ii];
-      }
-      for (int ii = ma - 1; ii >= 0; --ii) {
-        double v = wl[ii];
-        for (int jj = ii + 1; jj < ma; ++jj) v -= Sm[jj * WMA + ii] * wl[jj];
-        wl[ii] = v / Sm[ii * WMA + ii];
-      }
-    }
+    if (t == 0) schur_solve(Sm, WMA, ma, wl);   // dlam = S^-1 wl
     __syncthreads();
     for (int p = t; p < k; p += T) {
       double v = t2[p];
@@ -1391,53 +1337,14 @@ __device__ __forceinline__ void pg_solve_date(int b, const pq_problem& pb, const
     for (int p = t; p < k; p += T) xF[p] += t2[p];
     if (t < ma) lamv[t] += wl[t];
     __syncthreads();
-    WSTAMP(4);
+    PG_STAMP(R, 12);
   }
-  // ---- inner primal step: the free variables outside their box, fixed at the bound they
-  // cross (k_pg_post's test), the others compacted in order; the reduced rhs and the active
-  // rows' rhs take the fixed values (the P_FB columns are K's columns) -------------------------
+  // ---- inner primal step (pg_fix_violators) ---------------------------------------------------
   if (it_in >= inner || !has_box) break;   // uniform
   {
     int* iw = reinterpret_cast<int*>(sc4 + 2 * KS);   // 4 x KS ints in the free half of sc4
-    int* s_m2 = iw;             // kept: K position
-    int* s_f2 = iw + KS;        // kept: variable
-    int* s_vp = iw + 2 * KS;    // violator: K position
-    int* s_vi = iw + 3 * KS;    // violator: 4 variable + bound side (1 lower, 2 upper)
-    double* s_vv = rx;          // violator: bound value
-    if (w == 0) {
-      int nk = 0, nv = 0;
-      for (int p0 = 0; p0 < k; p0 += 64) {
-        const int p = p0 + l;
-        int f = 0, i = 0;
-        double v = 0.0;
-        if (p < k) {
-          i = wk.Fl[p];
-          const double xi = xF[p];
-          if (!isinf(lb[i]) && xi < lb[i] - 1e-12 * (1.0 + fabs(lb[i]))) { f = 1; v = lb[i]; }
-          else if (!isinf(ub[i]) && xi > ub[i] + 1e-12 * (1.0 + fabs(ub[i]))) { f = 2; v = ub[i]; }
-        }
-        const unsigned long long mv = __ballot(p < k && f != 0);
-        const unsigned long long mk = __ballot(p < k && f == 0);
-        const unsigned long long below = (1ull << l) - 1ull;
-        if (p < k && f != 0) {
-          const int j = nv + __popcll(mv & below);
-          s_vp[j] = s_map[p];
-          s_vi[j] = 4 * i + f;
-          s_vv[j] = v;
-        } else if (p < k) {
-          const int j = nk + __popcll(mk & below);
-          s_m2[j] = s_map[p];
-          s_f2[j] = i;
-          t1[j] = xF[p];
-          t2[j] = wk.rF[p];
-        }
-        nv += __popcll(mv);
-        nk += __popcll(mk);
-      }
-      if (l == 0) s_flag = nv;
-    }
-    __syncthreads();
-    const int nv = s_flag;
+    const PgFixLds fx{xF, s_map, iw, iw + KS, t1, t2, iw + 2 * KS, iw + 3 * KS, rx, s_al, dAv, &s_flag};
+    const int nv = pg_fix_violators<T, 0>(t, fx, wk, K, ldk, lb, ub, Cg, ld, ma, k, R);
 #ifdef PQ_PROFILE
     if (t == 0) {   // inner-step counters: solves, steps taken, violators, steps over WMA rows
       R[20] += 1.0;
@@ -1448,49 +1355,11 @@ __device__ __forceinline__ void pg_solve_date(int b, const pq_problem& pb, const
     }
 #endif
     if (nv == 0 || nv == k) break;   // uniform: feasible, or nothing left free (the rounds decide)
-    const int k2 = k - nv;
-    for (int p = t; p < k2; p += T) {
-      const int mp = s_m2[p];
-      double r = t2[p];
-      for (int j = 0; j < nv; ++j)
-        if (s_vv[j] != 0.0) r = fma(-K[(int64_t)mp * ldk + s_vp[j]], s_vv[j], r);
-      wk.rF[p] = r;
-      wk.Fl[p] = s_f2[p];
-      s_map[p] = mp;
-      xF[p] = t1[p];
-    }
-    for (int j = t; j < nv; j += T) {
-      const int i = s_vi[j] >> 2;
-      wk.fl[i] = s_vi[j] & 3;
-      wk.xb[i] = s_vv[j];
-    }
-    for (int a = w; a < ma; a += NW) {
-      const double* cr = Cg + (int64_t)s_al[a] * ld;
-      double sum = 0.0;
-      for (int j = l; j < nv; j += 64) sum += cr[s_vi[j] >> 2] * s_vv[j];
-      sum = wave_sum(sum);
-      if (l == 0) dAv[a] -= sum;
-    }
-    if (t == 0) R[R_K] = k2;
-    k = k2;
-    __syncthreads();
+    k -= nv;
   }
   }   // inner primal loop
-  // ---- expand: xs = x_B off F, x_F on F; general multipliers by row ------------------------
-  for (int ii = t; ii < n; ii += T) wk.xs[ii] = wk.xb[ii];
-  __syncthreads();
-  for (int p = t; p < k; p += T) {
-    wk.xs[wk.Fl[p]] = xF[p];
-    wk.solx[p] = xF[p];
-  }
-  if (t < 64) R[R_LAM + t] = 0.0;   // the 64 row slots
-  __syncthreads();
-  if (t < ma) {
-    R[R_LAM + s_al[t]] = lamv[t];
-    R[R_SOL + t] = lamv[t];
-  }
-  WSTAMP(5);
-#undef WSTAMP
+  pg_expand<T>(t, wk, n, k, xF, ma, s_al, lamv, R);
+  PG_STAMP(R, 13);
 }
 
 // A resident grid strides over the bucket's list of dates (k_pg_form appends them) -- with one
@@ -1545,21 +1414,14 @@ __device__ __forceinline__ void pg_big_date(int b, const pq_lowrank& lr, const p
   const int nbk = (k + TB - 1) / TB;
   const int kp = nbk * TB;
 #ifdef PQ_PROFILE
-  long long tb_last_ = wall_clock64();
-#define BSTAMP(k_)                                                         \
-  do {                                                                     \
-    __syncthreads();                                                       \
-    if (t == 0) { const long long n_ = wall_clock64(); R[25 + (k_)] += (double)(n_ - tb_last_); tb_last_ = n_; } \
-  } while (0)
-#else
-#define BSTAMP(k_) do { } while (0)
+  long long t_last_ = wall_clock64();   // (PG_STAMP slots 25..29)
 #endif
   // P_FF (both triangles) and the reduced rhs rF = -q_F - p_scale (w_scale Xc'Xc x_B)_F come
   // from k_pg_form<PG_KBIG> on the same stream; FormW reads the diagonal 64 x 64 blocks in
   // full and the other originals from the upper half, which the factor leaves untouched
   const int info = wg_cholesky<false>(FormW{K, ldk, k, delta}, K, ldk, nbk, k, Dt, smem);
   if (t == 0) R[R_FORMED] = 0.0;   // the lower tiles now hold L: no reuse of this P_FF
-  BSTAMP(0);
+  PG_STAMP(R, 25);
   if (info) {
     if (t == 0) R[R_STATE] = PQ_PG_FALLBACK;
     return;
@@ -1598,31 +1460,9 @@ __device__ __forceinline__ void pg_big_date(int b, const pq_lowrank& lr, const p
                 Y2_OFF = T2_OFF + 2 * TB;
   static_assert(Y2_OFF + 8 * TB <= CHOL_LDS, "k_pg_big LDS layout (two-right-hand-side solve)");
   auto factor_s = [&]() -> bool {   // S = U'U + delta I and its Cholesky; true: not PD (uniform)
-    for (int e = w; e < ma * ma; e += PW) {
-      const int ii = e / ma, jj = e % ma;
-      if (jj > ii) continue;
-      double sum = 0.0;
-      for (int p = l; p < k; p += 64) sum += U[(int64_t)ii * ld + p] * U[(int64_t)jj * ld + p];
-      sum = wave_sum(sum);
-      if (l == 0) Sm[ii * WMA + jj] = sum + (ii == jj ? delta : 0.0);
-    }
+    pg_schur<PT>(t, U, ld, k, ma, delta, Sm, WMA);
     __syncthreads();
-    if (t == 0) {
-      int sbad = 0;
-      for (int c = 0; c < ma && !sbad; ++c) {
-        double d = Sm[c * WMA + c];
-        for (int m = 0; m < c; ++m) d -= Sm[c * WMA + m] * Sm[c * WMA + m];
-        if (!(d > 0.0) || !isfinite(d)) { sbad = 1; break; }
-        d = sqrt(d);
-        Sm[c * WMA + c] = d;
-        for (int r = c + 1; r < ma; ++r) {
-          double v = Sm[r * WMA + c];
-          for (int m = 0; m < c; ++m) v -= Sm[r * WMA + m] * Sm[c * WMA + m];
-          Sm[r * WMA + c] = v / d;
-        }
-      }
-      red[0] = sbad;
-    }
+    if (t == 0) red[0] = schur_potrf(Sm, WMA, ma);
     __syncthreads();
     return red[0] != 0.0;
   };
@@ -1642,8 +1482,8 @@ __device__ __forceinline__ void pg_big_date(int b, const pq_lowrank& lr, const p
   }
   for (int p = t; p < kp; p += PT) sx[p] = p < k ? wk.solx[p] : 0.0;
   __syncthreads();
-  BSTAMP(1);
-  // ---- proximal iterative refinement (polish_w.hip, compact mode) ------------------------------
+  PG_STAMP(R, 26);
+  // ---- proximal iterative refinement (the rules of polish_rules.h) -------------------------------
   for (int itr = 0; itr < s.refine_iters; ++itr) {
     {   // rx = rF - P_FF x - C_aF' lam.  P_FF x in one coalesced pass over the stored originals
         // (the diagonal 64-blocks in full, the off-diagonal blocks in the upper half): row i's
@@ -1712,20 +1552,17 @@ __device__ __forceinline__ void pg_big_date(int b, const pq_lowrank& lr, const p
       double sum = 0.0;
       for (int p = l; p < k; p += 64) sum += c[wk.Fl[p]] * sx[p];
       sum = wave_sum(sum);
-      if (l == 0) {
-        const double v = dAv[a] - sum;
-        rl[a] = fabs(v) <= 1e-14 * (1.0 + fabs(dAv[a]) + fabs(sum)) ? 0.0 : v;
-      }
+      if (l == 0) rl[a] = row_residual(dAv[a], sum);
     }
     __syncthreads();
     double rm = 0.0;
     for (int p = t; p < k; p += PT) rm = fmax(rm, fabs(rx[p]));
     if (t < ma) rm = fmax(rm, fabs(rl[t]));
-    BSTAMP(2);
+    PG_STAMP(R, 27);
     // (with defer_u this break can come before U and S exist: the starting point then already
-    // solves the regularised KKT system to 1e-13 of the problem scale and is kept as it is --
-    // no step is taken, so S's Cholesky, which only guards the step, is not needed)
-    if (block_max(rm, red) <= 1e-13 * sc) break;
+    // solves the regularised KKT system to POLISH_STOP_REL of the problem scale and is kept as it
+    // is -- no step is taken, so S's Cholesky, which only guards the step, is not needed)
+    if (refine_done(block_max(rm, red), sc)) break;
     if (defer_u && itr == 0) {   // t1 = L^-1 rx and U = L^-1 C_aF' in one pass, then S
       double* cr2 = smem + CR_OFF;
       double* u1 = smem + U1_OFF;
@@ -1749,18 +1586,7 @@ __device__ __forceinline__ void pg_big_date(int b, const pq_lowrank& lr, const p
       if (l == 0) wl[a] = sum - rl[a];
     }
     __syncthreads();
-    if (t == 0) {   // dlam = S^-1 wl
-      for (int ii = 0; ii < ma; ++ii) {
-        double v = wl[ii];
-        for (int jj = 0; jj < ii; ++jj) v -= Sm[ii * WMA + jj] * wl[jj];
-        wl[ii] = v / Sm[ii * WMA + ii];
-      }
-      for (int ii = ma - 1; ii >= 0; --ii) {
-        double v = wl[ii];
-        for (int jj = ii + 1; jj < ma; ++jj) v -= Sm[jj * WMA + ii] * wl[jj];
-        wl[ii] = v / Sm[ii * WMA + ii];
-      }
-    }
+    if (t == 0) schur_solve(Sm, WMA, ma, wl);   // dlam = S^-1 wl
     __syncthreads();
     for (int p = t; p < kp; p += PT) {   // t1 <- t1 - U dlam ; dx = L^-T t1
       double v = t1[p];
@@ -1772,27 +1598,14 @@ __device__ __forceinline__ void pg_big_date(int b, const pq_lowrank& lr, const p
     for (int p = t; p < k; p += PT) sx[p] += dx[p];
     if (t < ma) lamv[t] += wl[t];
     __syncthreads();
-    BSTAMP(3);
+    PG_STAMP(R, 28);
   }
-  // ---- expand: xs = x_B off F, x_F on F; general multipliers by row ------------------------
-  for (int ii = t; ii < n; ii += PT) wk.xs[ii] = wk.xb[ii];
-  __syncthreads();
-  for (int p = t; p < k; p += PT) {
-    wk.xs[wk.Fl[p]] = sx[p];
-    wk.solx[p] = sx[p];
-  }
-  if (t < 64) R[R_LAM + t] = 0.0;
-  __syncthreads();
-  if (t < ma) {
-    R[R_LAM + s_al[t]] = lamv[t];
-    R[R_SOL + t] = lamv[t];
-  }
-  BSTAMP(4);
+  pg_expand<PT>(t, wk, n, k, sx, ma, s_al, lamv, R);
+  PG_STAMP(R, 29);
   if (t == 0) {
     R[30] += 1.0;
     R[31] += (double)k;
   }
-#undef BSTAMP
 }
 
 // a resident grid striding over the large free sets' list (k_pg_form<PG_KBIG>'s)
@@ -2232,10 +2045,9 @@ __global__ __launch_bounds__(PPT) void k_pg_post(pq_lowrank lr, pq_problem pb, p
       const int f = fv[j];
       const double lbi = lbv[j], ubi = ubv[j];
       if (f == 0 && has_box) {
-        if (!isinf(lbi) && xi < lbi - ptol * (1.0 + fabs(lbi))) { wk.fl[i] = 1; bad = 1; }
-        else if (!isinf(ubi) && xi > ubi + ptol * (1.0 + fabs(ubi))) { wk.fl[i] = 2; bad = 1; }
-      } else if (f == 1 && lbi != ubi && -gi > dtol) { wk.fl[i] = 0; bad = 1; }
-      else if (f == 2 && -gi < -dtol) { wk.fl[i] = 0; bad = 1; }
+        const int c = box_cross(xi, lbi, ubi, ptol);
+        if (c) { wk.fl[i] = c; bad = 1; }
+      } else if (bound_release(f, lbi, ubi, gi, dtol)) { wk.fl[i] = 0; bad = 1; }
       else if (soft > 0.0 && f == 1 && lbi != ubi && -gi > dtol - soft) wk.fl[i] = 5;   // near the sign
       else if (soft > 0.0 && f == 2 && -gi < soft - dtol) wk.fl[i] = 6;                  // (resolved below)
     }
@@ -2259,11 +2071,8 @@ __global__ __launch_bounds__(PPT) void k_pg_post(pq_lowrank lr, pq_problem pb, p
     if (hl == 0) {
       if (lg[r] != ug[r]) {
         const int a = (int)R[R_ACT + r];
-        const double lam = lamof(r);
-        if (a == 0 && sum > ug[r] + ptol * (1.0 + fabs(ug[r]))) { R[R_ACT + r] = 2; bad = 1; }
-        else if (a == 0 && sum < lg[r] - ptol * (1.0 + fabs(lg[r]))) { R[R_ACT + r] = 1; bad = 1; }
-        else if (a == 2 && lam < -dtol) { R[R_ACT + r] = 0; bad = 1; }
-        else if (a == 1 && lam > dtol) { R[R_ACT + r] = 0; bad = 1; }
+        const int a2 = row_verdict(a, sum, lg[r], ug[r], lamof(r), ptol, dtol);
+        if (a2 != a) { R[R_ACT + r] = a2; bad = 1; }
       } else if (fabs(sum - ug[r]) > 1e-10 * (1.0 + fabs(ug[r]))) {
         bad = 1;
       }

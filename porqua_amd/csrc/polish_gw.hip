@@ -15,8 +15,8 @@
 //                          S dlam = B t - rl with S = B K^-1 B' + delta I (per date, from
 //                          the bordered rows' own K^-1 images computed once per round),
 //                          dx = K^-1 (r - B' dlam) (pass 2), x += dx, lam += dlam.
-// That is polish_w.hip's Woodbury mode (same regularised system, same refinement, same
-// tolerances) with the window passes shared by the group's dates instead of repeated per
+// That is polish_w.hip's Woodbury mode (same regularised system, the refinement rules of
+// polish_rules.h) with the window passes shared by the group's dates instead of repeated per
 // date.  The exact P x / checks / scoring of the round follow in polish_g.hip's passes.
 //
 // Replaces, with polish_g.hip, the accuracy of qpsolvers' interior-point answer
@@ -24,6 +24,7 @@
 #include "common.h"
 #include "capi_util.h"
 #include "pg_record.h"
+#include "polish_rules.h"
 
 namespace pq {
 
@@ -490,22 +491,7 @@ __global__ __launch_bounds__(YT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   }
   __syncthreads();
   if (t < G && g_on[t]) {   // Cholesky of S (lower, in place), one thread per date
-    double* S = g_S + t * YMB * YMB;
-    const int mb = g_mb[t];
-    int bad = 0;
-    for (int cI = 0; cI < mb && !bad; ++cI) {
-      double dd = S[cI * YMB + cI];
-      for (int k = 0; k < cI; ++k) dd -= S[cI * YMB + k] * S[cI * YMB + k];
-      if (!(dd > 0.0) || !isfinite(dd)) { bad = 1; break; }
-      dd = sqrt(dd);
-      S[cI * YMB + cI] = dd;
-      for (int r = cI + 1; r < mb; ++r) {
-        double v = S[r * YMB + cI];
-        for (int k = 0; k < cI; ++k) v -= S[r * YMB + k] * S[cI * YMB + k];
-        S[r * YMB + cI] = v / dd;
-      }
-    }
-    if (bad) {   // left for the per-date kernel
+    if (schur_potrf(g_S + t * YMB * YMB, YMB, g_mb[t])) {   // left for the per-date kernel
       rec[(int64_t)(d0 + t) * PGR + R_STATE] = PQ_PG_FALLBACK;
       g_on[t] = g_run[t] = 0;
     }
@@ -574,13 +560,12 @@ __global__ __launch_bounds__(YT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
           bx = wk.xs[i];
         }
         const double dBj = g_dB[m * YMB + j];
-        const double v = dBj - bx;
-        const double rl = fabs(v) <= 1e-14 * (1.0 + fabs(dBj) + fabs(bx)) ? 0.0 : v;
+        const double rl = row_residual(dBj, bx);
         g_rl[m * YMB + j] = rl;
         rm = fmax(rm, fabs(rl));
       }
       g_mur[m] = mur;
-      if (rm <= 1e-13 * g_sc[m] || it == nref) g_run[m] = 0;   // converged (or out of steps)
+      if (refine_done(rm, g_sc[m]) || it == nref) g_run[m] = 0;   // converged (or out of steps)
     }
     __syncthreads();
     if (t == 0) {
@@ -622,16 +607,7 @@ __global__ __launch_bounds__(YT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         wl[j] = tj - g_rl[m * YMB + j];
       }
       const double* S = g_S + m * YMB * YMB;
-      for (int i = 0; i < mb; ++i) {
-        double v = wl[i];
-        for (int j = 0; j < i; ++j) v -= S[i * YMB + j] * wl[j];
-        wl[i] = v / S[i * YMB + i];
-      }
-      for (int i = mb - 1; i >= 0; --i) {
-        double v = wl[i];
-        for (int j = i + 1; j < mb; ++j) v -= S[j * YMB + i] * wl[j];
-        wl[i] = v / S[i * YMB + i];
-      }
+      schur_solve(S, YMB, mb, wl);
       double suf = g_su[m];
       for (int j = 0; j < YMB; ++j) {
         if (j >= mb) break;

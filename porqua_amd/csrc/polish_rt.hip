@@ -22,14 +22,13 @@
 // before the factorisation: it is accumulated from the tile values while they are loaded
 // (row sums of every lower tile, column sums of the off-diagonal ones), so the solve reads
 // the K scratch once per factorisation.  Everything else -- the active rows' Schur block,
-// the acceptance of the refinement, the inner primal step and the outputs -- is
-// k_pg_solve's (polish_g.hip), so the pipeline's other kernels see the same record.
+// the acceptance of the refinement, the inner primal step and the outputs -- is shared with
+// k_pg_solve (polish_rules.h, pg_solve_dev.h), so the pipeline's other kernels see the same record.
 // Replaces, with the rest of the grouped polish, the accuracy of qpsolvers' answer
 // (src/qp_problems.py:211-214).
 #include <cstdlib>
 
-#include "polish_dev.h"
-#include "pg_record.h"
+#include "pg_solve_dev.h"
 
 namespace pq {
 namespace {
@@ -288,25 +287,18 @@ __device__ __forceinline__ void rt_solve_date(int b, const pq_problem& pb, const
   const double* ub = has_box ? pb.ub + (int64_t)b * pb.box_stride : nullptr;
   __syncthreads();
 #ifdef PQ_PROFILE
-  long long t_last_ = wall_clock64();
-#define RSTAMP(k_)                                                         \
-  do {                                                                     \
-    __syncthreads();                                                       \
-    if (t == 0) { const long long n_ = wall_clock64(); R[8 + (k_)] += (double)(n_ - t_last_); t_last_ = n_; } \
-  } while (0)
-#else
-#define RSTAMP(k_) do { } while (0)
+  long long t_last_ = wall_clock64();   // (PG_STAMP slots 8..13, as pg_solve_date)
 #endif
   f64x4 S[NT];
   for (int it_in = 0;; ++it_in) {
     const int l = threadIdx.x + loop_zero();
     rt_load<NB>(S, K, ldk, s_map, k, delta, xF, px);
-    RSTAMP(0);
+    PG_STAMP(R, 8);
     if (rt_potrf<NB>(S, k, tsc)) {
       if (l == 0) R[R_STATE] = PQ_PG_FALLBACK;
       return;
     }
-    RSTAMP(1);
+    PG_STAMP(R, 9);
     // U = L^-1 C_aF' (rows a of the U scratch), S = U'U + delta I
     for (int a = 0; a < ma; ++a) {
       const double* cr = Cg + (int64_t)s_al[a] * ld;
@@ -316,40 +308,16 @@ __device__ __forceinline__ void rt_solve_date(int b, const pq_problem& pb, const
       for (int p = l; p < k; p += 64) wk.U[(int64_t)a * ld + p] = t2[p];
       __syncthreads();
     }
-    for (int e = 0; e < ma * ma; ++e) {
-      const int ii = e / ma, jj = e % ma;
-      if (jj > ii) continue;
-      const double* ui = wk.U + (int64_t)ii * ld;
-      const double* uj = wk.U + (int64_t)jj * ld;
-      double sum = 0.0;
-      for (int p = l; p < k; p += 64) sum += ui[p] * uj[p];
-      sum = wave_sum(sum);
-      if (l == 0) Sm[ii * RT_WMA + jj] = sum + (ii == jj ? delta : 0.0);
-    }
+    pg_schur<64>(l, wk.U, ld, k, ma, delta, Sm, RT_WMA);
     __syncthreads();
-    if (l == 0) {   // tiny Cholesky of S (ma <= 8), one lane
-      int sbad = 0;
-      for (int c = 0; c < ma && !sbad; ++c) {
-        double d = Sm[c * RT_WMA + c];
-        for (int m = 0; m < c; ++m) d -= Sm[c * RT_WMA + m] * Sm[c * RT_WMA + m];
-        if (!(d > 0.0) || !isfinite(d)) { sbad = 1; break; }
-        d = sqrt(d);
-        Sm[c * RT_WMA + c] = d;
-        for (int r = c + 1; r < ma; ++r) {
-          double v = Sm[r * RT_WMA + c];
-          for (int m = 0; m < c; ++m) v -= Sm[r * RT_WMA + m] * Sm[c * RT_WMA + m];
-          Sm[r * RT_WMA + c] = v / d;
-        }
-      }
-      s_flag = sbad;
-    }
+    if (l == 0) s_flag = schur_potrf(Sm, RT_WMA, ma);
     __syncthreads();
     if (s_flag) {
       if (l == 0) R[R_STATE] = PQ_PG_FALLBACK;
       return;
     }
-    RSTAMP(2);
-    // ---- proximal iterative refinement (k_pg_solve's) -------------------------------------
+    PG_STAMP(R, 10);
+    // ---- proximal iterative refinement (the rules of polish_rules.h) -----------------------
     for (int itr = 0; itr < s.refine_iters; ++itr) {
       if (itr > 0) {   // later steps: P_FF x from the K scratch (the first has it from the load)
         for (int p = l; p < k; p += 64) {
@@ -364,10 +332,7 @@ __device__ __forceinline__ void rt_solve_date(int b, const pq_problem& pb, const
         double sum = 0.0;
         for (int p = l; p < k; p += 64) sum += cr[wk.Fl[p]] * xF[p];
         sum = wave_sum(sum);
-        if (l == 0) {
-          const double v = dAv[a] - sum;
-          rl[a] = fabs(v) <= 1e-14 * (1.0 + fabs(dAv[a]) + fabs(sum)) ? 0.0 : v;
-        }
+        if (l == 0) rl[a] = row_residual(dAv[a], sum);
       }
       __syncthreads();
       double rm = 0.0;
@@ -383,8 +348,8 @@ __device__ __forceinline__ void rt_solve_date(int b, const pq_problem& pb, const
       }
       if (l < ma) rm = fmax(rm, fabs(rl[l]));
       __syncthreads();
-      RSTAMP(3);
-      if (wave_max(rm) <= 1e-13 * sc) break;   // uniform
+      PG_STAMP(R, 11);
+      if (refine_done(wave_max(rm), sc)) break;   // uniform
       rt_fwd<NB>(S, k, rx, t2);   // t2 = L^-1 rx
       for (int a = 0; a < ma; ++a) {   // wl = U' t2 - rl
         const double* ua = wk.U + (int64_t)a * ld;
@@ -394,18 +359,9 @@ __device__ __forceinline__ void rt_solve_date(int b, const pq_problem& pb, const
         if (l == 0) wl[a] = sum - rl[a];
       }
       __syncthreads();
-      if (l == 0) {   // dlam = S^-1 wl
-        for (int ii = 0; ii < ma; ++ii) {
-          double v = wl[ii];
-          for (int jj = 0; jj < ii; ++jj) v -= Sm[ii * RT_WMA + jj] * wl[jj];
-          wl[ii] = v / Sm[ii * RT_WMA + ii];
-        }
-        for (int ii = ma - 1; ii >= 0; --ii) {
-          double v = wl[ii];
-          for (int jj = ii + 1; jj < ma; ++jj) v -= Sm[jj * RT_WMA + ii] * wl[jj];
-          wl[ii] = v / Sm[ii * RT_WMA + ii];
-        }
-      }
+      // dlam = S^-1 wl (through L_'s pointers: with the local copies the kernel's scratch grows by
+      // 44 B/lane, profiles/polish_rules_resource_usage.txt)
+      if (l == 0) schur_solve(L_.Sm, RT_WMA, ma, L_.wl);
       __syncthreads();
       for (int p = l; p < KS; p += 64) {
         double v = p < k ? t2[p] : 0.0;
@@ -417,42 +373,13 @@ __device__ __forceinline__ void rt_solve_date(int b, const pq_problem& pb, const
       for (int p = l; p < k; p += 64) xF[p] += t2[p];
       if (l < ma) lamv[l] += wl[l];
       __syncthreads();
-      RSTAMP(4);
+      PG_STAMP(R, 12);
     }
-    // ---- inner primal step (k_pg_solve's): free variables outside their box fixed at the
-    // bound they cross, the others compacted in order, the reduced rhs updated -----------------
+    // ---- inner primal step (pg_fix_violators; s_map / xF stay zero-padded up to KS) ------------
     if (it_in >= inner || !has_box) break;   // uniform
     {
-      int nk = 0, nv = 0;
-      for (int p0 = 0; p0 < k; p0 += 64) {
-        const int p = p0 + l;
-        int f = 0, i = 0;
-        double v = 0.0;
-        if (p < k) {
-          i = wk.Fl[p];
-          const double xi = xF[p];
-          if (!isinf(lb[i]) && xi < lb[i] - 1e-12 * (1.0 + fabs(lb[i]))) { f = 1; v = lb[i]; }
-          else if (!isinf(ub[i]) && xi > ub[i] + 1e-12 * (1.0 + fabs(ub[i]))) { f = 2; v = ub[i]; }
-        }
-        const unsigned long long mv = __ballot(p < k && f != 0);
-        const unsigned long long mk = __ballot(p < k && f == 0);
-        const unsigned long long below = (1ull << l) - 1ull;
-        if (p < k && f != 0) {
-          const int j = nv + __popcll(mv & below);
-          s_vp[j] = s_map[p];
-          s_vi[j] = 4 * i + f;
-          vv[j] = v;
-        } else if (p < k) {
-          const int j = nk + __popcll(mk & below);
-          s_m2[j] = s_map[p];
-          s_f2[j] = i;
-          t1[j] = xF[p];
-          t2[j] = wk.rF[p];
-        }
-        nv += __popcll(mv);
-        nk += __popcll(mk);
-      }
-      __syncthreads();
+      const PgFixLds fx{xF, s_map, s_m2, s_f2, t1, t2, s_vp, s_vi, vv, s_al, dAv, &s_flag};
+      const int nv = pg_fix_violators<64, KS>(l, fx, wk, K, ldk, lb, ub, Cg, ld, ma, k, R);
 #ifdef PQ_PROFILE
       if (t == 0) {   // inner-step counters: solves, steps taken, violators, (unused), k at the check
         R[20] += 1.0;
@@ -462,54 +389,11 @@ __device__ __forceinline__ void rt_solve_date(int b, const pq_problem& pb, const
       }
 #endif
       if (nv == 0 || nv == k) break;   // uniform: feasible, or nothing left free (the rounds decide)
-      const int k2 = k - nv;
-      for (int p = l; p < KS; p += 64) {
-        if (p < k2) {
-          const int mp = s_m2[p];
-          double r = t2[p];
-          for (int j = 0; j < nv; ++j)
-            if (vv[j] != 0.0) r = fma(-K[(int64_t)mp * ldk + s_vp[j]], vv[j], r);
-          wk.rF[p] = r;
-          wk.Fl[p] = s_f2[p];
-          s_map[p] = mp;
-          xF[p] = t1[p];
-        } else {
-          s_map[p] = 0;
-          xF[p] = 0.0;
-        }
-      }
-      for (int j = l; j < nv; j += 64) {
-        const int i = s_vi[j] >> 2;
-        wk.fl[i] = s_vi[j] & 3;
-        wk.xb[i] = vv[j];
-      }
-      for (int a = 0; a < ma; ++a) {
-        const double* cr = Cg + (int64_t)s_al[a] * ld;
-        double sum = 0.0;
-        for (int j = l; j < nv; j += 64) sum += cr[s_vi[j] >> 2] * vv[j];
-        sum = wave_sum(sum);
-        if (l == 0) dAv[a] -= sum;
-      }
-      if (l == 0) R[R_K] = k2;
-      k = k2;
-      __syncthreads();
+      k -= nv;
     }
   }
-  // ---- expand: xs = x_B off F, x_F on F; general multipliers by row ------------------------
-  for (int ii = t; ii < n; ii += 64) wk.xs[ii] = wk.xb[ii];
-  __syncthreads();
-  for (int p = t; p < k; p += 64) {
-    wk.xs[wk.Fl[p]] = xF[p];
-    wk.solx[p] = xF[p];
-  }
-  R[R_LAM + t] = 0.0;   // the 64 row slots
-  __syncthreads();
-  if (t < ma) {
-    R[R_LAM + s_al[t]] = lamv[t];
-    R[R_SOL + t] = lamv[t];
-  }
-  RSTAMP(5);
-#undef RSTAMP
+  pg_expand<64>(t, wk, n, k, xF, ma, s_al, lamv, R);
+  PG_STAMP(R, 13);
 }
 
 // One launch for the four register buckets (one wave per date): workgroups [0, B) take the

@@ -163,6 +163,7 @@ def problem_scale(X, mu, psw, p_diag, q):
 
 STOP_REL = 1e-13      # the polish kernels end the refinement at a residual of STOP_REL x problem scale ...
 ROW_ZERO = 1e-14      # ... with a row residual within ROW_ZERO (1 + |d_a| + |C_aF x_F|) taken as zero
+# (the kernels' copies: POLISH_STOP_REL, POLISH_ROW_ZERO in porqua_amd/csrc/polish_rules.h)
 
 
 def reduced_kkt_f64(X, mu, psw, p_diag, q, C, lg, ug, lb, ub, side, act, x0, lam0, delta, refine, stop=None):

@@ -5,6 +5,8 @@ x*_F well inside the box), the float64 yardstick reduced_kkt_f64 started 1e-7 aw
 the 1e-9 its bar is designed to stay under, and the engine's algorithm restated in numpy
 (tests/engine_model.py) recovers F and x* from its own ADMM stop."""
 import functools
+import os
+import re
 
 import numpy as np
 import pytest
@@ -137,3 +139,15 @@ def test_engine_model_recovers_the_free_set(fam, d):
     assert np.array_equal(np.flatnonzero(zb == 0.0), o.F)
     assert err <= 1e-9, err
     assert np.abs(lam - o.lam).max() <= 1e-9 * o.s and np.abs(zb - o.z).max() <= 1e-9 * o.s
+
+
+def test_the_kernels_rules_header_states_the_models_constants():
+    """The constants every polish kernel takes from porqua_amd/csrc/polish_rules.h are the ones this
+    model states (STOP_REL, ROW_ZERO), read from the header itself; the inner step's box tolerance is 1e-12."""
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "porqua_amd", "csrc",
+                        "polish_rules.h")
+    found = dict(re.findall(r"^constexpr double (POLISH_\w+) = ([0-9.eE+-]+);", open(path).read(), flags=re.M))
+    assert set(found) == {"POLISH_STOP_REL", "POLISH_ROW_ZERO", "POLISH_INNER_BOX_TOL"}, found
+    assert float(found["POLISH_STOP_REL"]) == mf.STOP_REL
+    assert float(found["POLISH_ROW_ZERO"]) == mf.ROW_ZERO
+    assert float(found["POLISH_INNER_BOX_TOL"]) == 1e-12
