@@ -774,6 +774,40 @@ int pq_window_project_batched(const double* panel, int64_t ldp, int32_t n, const
                               const int32_t* kcnt, int32_t kmax, const int32_t* frow, double* F, int64_t ldf,
                               void* stream);
 
+/* Gerber covariance (Gerber, Markowitz, Ernst, Miao, Javid, Sargen 2022; Riskfolio-Lib's gerber1 /
+ * gerber2) of every date.  X is date b's T x n window of raw returns (not demeaned), read exactly
+ * as pq_cov_batched reads it (entries of rows[b] past tlen[b] are never read), dg (batch x
+ * dg_stride) its diag(Xc'Xc) as pq_window_sumsq leaves it, and 0 < threshold <= 1:
+ *   sd_k = sqrt(dg_k / (T - 1)),  h_k = threshold sd_k,
+ *   s_tk = +1 if x_tk >= h_k, -1 if x_tk <= -h_k, else 0,
+ *   a_k = sum_t |s_tk|,  H = S'S (= N^UU + N^DD - N^UD - N^DU),  P = |S|'|S|   (integers, exact),
+ *   variant 2: g_ij = H_ij / sqrt(a_i a_j) (positive semi-definite by construction; the product
+ *   exact in FP64);  variant 1: g_ij = H_ij / (a_i + a_j - P_ij), the paper's first form with the
+ *   denominator T - N^NN_ij formed in integers;
+ *   out_ij = g_ij (sd_i sd_j), or g_ij alone where corr != 0.
+ * Two kernels: the sign kernel (stages & 1; per 64 assets and date) thresholds the window and
+ * writes the int8 signs asset-major into St, batch x round_up(n, 64) x round_up(tmax, 64) bytes
+ * (16-byte aligned scratch, zeros past the window and past n), the counts a (int32, batch x ldc,
+ * zeros in [n, ldc)) and status; the Gram kernel (stages & 2; per 64 x 64 output tile and date)
+ * forms H, and for variant 1 P from the same fragments, with v_mfma_i32_16x16x64_i8 (a window is
+ * ceil(T / 64) steps of it) and writes out in FP64.  stages = 3 runs both; 2 alone reads the St,
+ * counts and status an earlier stages = 1 call with the same arguments left.  out is batch x ld x
+ * ld (date stride out_stride); only [0, n) x [0, n) of a date is written, symmetric bit for bit.
+ * status[b]: PQ_GERBER_OK, or PQ_GERBER_BAD_INPUT -- T < 2, a non-finite value in the window, some
+ * dg_k not finite and > 0 (a constant column), some a_k = 0 --, for which the date's n x n block is
+ * NaN; nothing faults and no date affects another.  No floating-point atomics: the same input
+ * gives the same bits.
+ * 1 <= tmax <= PQ_GERBER_TMAX, n >= 1, ldp, dg_stride, ldc, ld >= n.  The call does not
+ * synchronise; only host-checkable arguments (null pointers, the sizes, variant outside {1, 2},
+ * threshold outside (0, 1], stages outside 1..3) return an error, and then nothing is launched. */
+#define PQ_GERBER_OK 0
+#define PQ_GERBER_BAD_INPUT 1
+#define PQ_GERBER_TMAX 1024
+int pq_gerber_cov_batched(const double* panel, int64_t ldp, int32_t n, const int32_t* rows, const int32_t* tlen,
+                          int32_t tmax, int32_t batch, const double* dg, int64_t dg_stride, double threshold,
+                          int32_t variant, int32_t corr, int32_t stages, int8_t* St, int32_t* counts, int64_t ldc,
+                          double* out, int32_t ld, int64_t out_stride, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

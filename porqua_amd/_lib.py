@@ -48,6 +48,11 @@ PQ_PCA_TMAX = 1024
 PQ_PCA_KMAX = 64
 PQ_PCA_OK, PQ_PCA_BAD_INPUT = range(2)
 
+# pq_gerber_cov_batched: per-date status, the longest window and the stages (include/porqua_hip.h)
+PQ_GERBER_OK, PQ_GERBER_BAD_INPUT = range(2)
+PQ_GERBER_TMAX = 1024
+PQ_GERBER_SIGNS, PQ_GERBER_GRAM = 1, 2
+
 PQ_PG_RECORD = 384                  # doubles per problem of the grouped polish record
 PQ_PG_PASS_SCRATCH = 123537          # doubles per slide group of the split polish window passes
 PQ_PG_PENDING, PQ_PG_DONE, PQ_PG_FALLBACK, PQ_PG_SKIP = range(4)
@@ -261,6 +266,9 @@ _EXPORTS = {
                                 c_int64, c_dp], c_int32),
     "pq_window_project_batched": ([c_dp, c_int64, c_int32, c_dp, c_dp, c_int32, c_int32, c_dp, c_int64, c_dp,
                                    c_int32, c_int64, c_dp, c_dp, c_dp, c_int32, c_dp, c_dp, c_int64, c_dp], c_int32),
+    "pq_gerber_cov_batched": ([c_dp, c_int64, c_int32, c_dp, c_dp, c_int32, c_int32, c_dp, c_int64,
+                               ctypes.c_double, c_int32, c_int32, c_int32, c_dp, c_dp, c_int64, c_dp, c_int32,
+                               c_int64, c_dp, c_dp], c_int32),
 }
 
 _lib = None

@@ -14,7 +14,10 @@ towards mean(diag S) I with a data-driven intensity per window (engine.shrinkage
 three sums over the window's T x T Gram), and 'pca' is the statistical factor model
 (probabilistic PCA, sklearn's PCA.get_covariance()): the top ``n_factors`` principal components
 of the window kept, the rest of the spectrum replaced by one trace-preserving noise level
-(engine.pca_window_form).  ``estimate_batch`` is the batched backtest entry: all
+(engine.pca_window_form), and 'gerber' is the Gerber statistic (Gerber et al. 2022; Riskfolio-Lib's
+gerber1 / gerber2): co-movement counts of the raw returns beyond ``threshold`` window standard
+deviations in place of the second moments (engine.gerber_cov; spec ``threshold`` 0.5 and
+``variant`` 2 by default).  ``estimate_batch`` is the batched backtest entry: all
 rebalance dates of a device-resident panel at once, results left on the device.
 """
 from __future__ import annotations
@@ -59,10 +62,18 @@ class Covariance:
     ``n_factors_batch_`` / ``noise_variance_batch_`` the (B,) device tensors of the last
     ``window_form_pca``.  The estimate is Z'Z + sigma2 I with k factor rows Z: RiskParity and
     HierarchicalRiskParity solve on that k-row window form, the QP objectives on the dense
-    estimate (``estimate_batch_lr`` does not serve 'pca')."""
+    estimate (``estimate_batch_lr`` does not serve 'pca').
+
+    method 'gerber' (spec ``threshold`` in (0, 1], default 0.5, and ``variant`` 1 or 2, default 2;
+    anything else raises ValueError before the device is touched): the dense estimate of
+    engine.gerber_cov.  Its thresholds are the window's own standard deviations, so there is no
+    window form shared between dates: ``estimate_batch_lr`` serves it with ``materialise=True``
+    only.  Variant 2 is positive semi-definite by construction, variant 1 can be indefinite."""
 
     def __init__(self, spec: CovarianceSpecification = None, *args, **kwargs):
         self.spec = CovarianceSpecification(*args, **kwargs) if spec is None else spec
+        if self.spec["method"] == "gerber":
+            self.gerber_spec   # a bad threshold or variant is refused here, before any device work
         self.shrinkage_ = None
         self.shrinkage_batch_ = None
         self.n_factors_ = None
@@ -85,6 +96,8 @@ class Covariance:
             covmat, self.shrinkage_ = _cov_shrunk(X, method)
         elif method == "pca":
             covmat, self.n_factors_, self.noise_variance_ = _cov_pca(X, self.n_factors)
+        elif method == "gerber":
+            covmat = cov_gerber(X, *self.gerber_spec)
         else:
             raise NotImplementedError("This method is not implemented yet")
         if self.spec.get("check_positive_definite") and not isPD(covmat):
@@ -98,6 +111,13 @@ class Covariance:
         """The spec's ``n_factors`` of method 'pca' ('mp' where none is given)."""
         nf = self.spec.get("n_factors")
         return "mp" if nf is None else nf
+
+    @property
+    def gerber_spec(self):
+        """(threshold, variant) of method 'gerber' (0.5 and 2 where the spec gives none);
+        ValueError for a threshold outside (0, 1] or a variant other than 1 or 2."""
+        th, var = self.spec.get("threshold"), self.spec.get("variant")
+        return _gerber_check(0.5 if th is None else th, 2 if var is None else var)
 
     def window_form_pca(self, panel, rows, tlen):
         """method 'pca' for every window of the device row table: engine.pca_window_form's factor
@@ -136,6 +156,21 @@ class Covariance:
         if method == "pca":
             raise NotImplementedError("the 'pca' covariance is not a T-row window form: window_form_pca gives its "
                                       "factor form, estimate the dense matrix")
+        if method == "gerber":
+            threshold, variant = self.gerber_spec
+            if not materialise:
+                raise NotImplementedError("the 'gerber' covariance has no window form: its thresholds are the "
+                                          "standard deviations of each date's own window, so no rows are shared "
+                                          "between dates; estimate the dense matrix (materialise=True)")
+            if panel.has_nan:   # complete windows only: the serial loop reports it
+                return None, None, None, None
+            from . import engine
+            n = panel.n
+            if out is not None:   # the kernel writes [0, n) x [0, n) only: the padding of a dense P is zero
+                out[:, n:, :] = 0.0
+                out[:, :n, n:] = 0.0
+            S, _, _ = engine.gerber_cov(panel, rows, tlen, threshold=threshold, variant=variant, out=out)
+            return S, torch.zeros(int(rows.shape[0]), dtype=torch.float64, device=S.device), None, None
         if method not in ("pearson", "linear_shrinkage") + SHRINKAGE_METHODS:
             raise NotImplementedError("This method is not implemented yet")
         B, n = int(rows.shape[0]), panel.n
@@ -278,6 +313,40 @@ def _cov_pca(X, n_factors="mp"):
     if isinstance(X, pd.DataFrame):
         S = pd.DataFrame(S, index=X.columns, columns=X.columns)
     return S, int(form.tlen[0].item()), float(form.sigma2[0].item())
+
+
+def _gerber_check(threshold, variant):
+    """(threshold, variant) as (float, int); ValueError unless 0 < threshold <= 1 and variant is 1 or 2
+    (host arithmetic only: a spec is refused before anything touches the device)."""
+    if isinstance(variant, bool) or not isinstance(variant, (int, np.integer)) or variant not in (1, 2):
+        raise ValueError(f"gerber: variant = {variant!r} must be 1 or 2")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) \
+            or not 0.0 < float(threshold) <= 1.0:
+        raise ValueError(f"gerber: threshold = {threshold!r} must lie in (0, 1]")
+    return float(threshold), int(variant)
+
+
+def cov_gerber(X, threshold=0.5, variant=2):
+    """Gerber covariance (Gerber et al. 2022) of one complete window: engine.gerber_cov at batch
+    1.  ``threshold`` in (0, 1]: the multiple of an asset's window standard deviation beyond
+    which a day counts as a move; ``variant`` 2 (positive semi-definite) or 1 (the paper's first
+    form).  ValueError for a bad spec, missing values or a bad-input window."""
+    threshold, variant = _gerber_check(threshold, variant)
+    from . import _lib, engine
+    Xv = np.ascontiguousarray(X.to_numpy() if hasattr(X, "to_numpy") else X, dtype=np.float64)
+    if np.isnan(Xv).any():
+        raise ValueError("the gerber covariance needs complete windows")
+    T, n = Xv.shape
+    pan = engine.Panel(Xv)
+    rows, tlen = pan.rows_to_device(np.arange(T, dtype=np.int32)[None], np.array([T], dtype=np.int32))
+    S, status, _ = engine.gerber_cov(pan, rows, tlen, threshold=threshold, variant=variant)
+    if int(status[0].item()) != _lib.PQ_GERBER_OK:
+        raise ValueError("the gerber covariance: bad input (fewer than 2 rows, non-finite data, a constant column, "
+                         "or an asset that never moves beyond its threshold)")
+    S = S[0, :n, :n].cpu().numpy()
+    if isinstance(X, pd.DataFrame):
+        S = pd.DataFrame(S, index=X.columns, columns=X.columns)
+    return S
 
 
 def cov_ledoit_wolf(X):

@@ -2028,7 +2028,7 @@ HRP_CHUNK_BYTES = 2 << 30   # the dense covariance buffer of hrp_weights stays b
 
 def hrp_weights(panel: "Panel", rows, tlen, alpha=None, c=None, centred: bool = True, scale: float = 1.0,
                 linkage: bool = False, chunk_bytes: int = HRP_CHUNK_BYTES, plan: "SlidePlan | None" = None,
-                method: str = "single"):
+                method: str = "single", dense=None):
     """Hierarchical-risk-parity weights of every window (pq_hrp_linkage_batched): per date the
     tree of the correlation distance of Sigma = alpha S + c I as SciPy's linkage builds it,
     its leaves in pre-order and the recursive bisection of that order by inverse-variance cluster
@@ -2041,7 +2041,11 @@ def hrp_weights(panel: "Panel", rows, tlen, alpha=None, c=None, centred: bool = 
     Gram X'X, mode 1), formed per chunk of dates so that
     the dense buffer stays under ``chunk_bytes``; one kernel launch per chunk.  ``alpha`` / ``c``:
     scalars or one value per date, defaults 1 and 0.  ``plan``: a SlidePlan of the row table where
-    the caller has one (it covers the whole batch, so the batch has to fit one chunk).  At most
+    the caller has one (it covers the whole batch, so the batch has to fit one chunk).  ``dense``:
+    a callable (rows_chunk, tlen_chunk, out) -> S that forms the chunk's dense matrices in place
+    of Panel.cov (out: the first dates of the (per, ld, ld) buffer; the first n rows and columns
+    of S are read, and a NaN there makes the date PQ_HRP_BAD_INPUT), e.g. the Gerber estimate;
+    ``centred`` and ``plan`` are then unused.  At most
     _lib.PQ_HRP_NMAX assets.  Returns (x [B, n], order [B, n] int32, stats [B, 2] = x' Sigma x and
     the smallest gap between consecutive merge distances, status [B] int32: _lib.PQ_HRP_*), and
     with ``linkage`` also Z [B, n - 1, 4] in SciPy's layout, all on the device; a date whose
@@ -2075,13 +2079,65 @@ def hrp_weights(panel: "Panel", rows, tlen, alpha=None, c=None, centred: bool = 
     work = torch.empty((per, n, ld), dtype=F64, device=dev) if meth != _lib.PQ_HRP_SINGLE else None
     for b0 in range(0, B, per):
         b1 = min(B, b0 + per)
-        S = panel.cov(rows[b0:b1], tlen[b0:b1], mode=0 if centred else 1, out=buf[:b1 - b0], plan=plan)
+        if dense is not None:
+            S = dense(rows[b0:b1], tlen[b0:b1], buf[:b1 - b0])
+        else:
+            S = panel.cov(rows[b0:b1], tlen[b0:b1], mode=0 if centred else 1, out=buf[:b1 - b0], plan=plan)
         _lib.check(lib.pq_hrp_linkage_batched(_ptr(S), ld, n, b1 - b0, _ptr(alpha[b0:]), _ptr(c[b0:]), float(scale),
                                               meth, None if work is None else _ptr(work), ld,
                                               _ptr(x[b0:]), x.stride(0), _ptr(order[b0:]), order.stride(0),
                                               _ptr(Z[b0:]) if linkage and n > 1 else None, _ptr(stats[b0:]),
                                               _ptr(status[b0:]), _stream()), "pq_hrp_linkage_batched")
     return out
+
+
+GERBER_CHUNK_BYTES = 2 << 30   # the int8 sign panel of gerber_cov stays below this
+
+
+def gerber_cov(panel: "Panel", rows, tlen, threshold: float = 0.5, variant: int = 2, corr: bool = False, out=None,
+               chunk_bytes: int = GERBER_CHUNK_BYTES):
+    """The Gerber covariance (Gerber et al. 2022) of every window (pq_gerber_cov_batched): per date
+    the signs s_tk of the raw returns beyond ``threshold`` times the window's own standard
+    deviation, the exact co-movement counts H = S'S on the int8 matrix cores, and
+    Sigma_ij = g_ij sd_i sd_j with g_ij = H_ij / sqrt(a_i a_j) (``variant`` 2, positive
+    semi-definite) or H_ij / (T - N^NN_ij) (``variant`` 1); ``corr``: g itself.  ``rows`` / ``tlen``:
+    the device row table, at most _lib.PQ_GERBER_TMAX rows per window.  ``out``: a (B, ld, ld)
+    buffer, ld = round_up(n, 64), of which only [0, n) x [0, n) of every date is written (None: a
+    zero-filled one is allocated).  The int8 sign panel is scratch, allocated per chunk of dates so
+    that it stays under ``chunk_bytes``.  Returns (S [B, ld, ld], status [B] int32: _lib.PQ_GERBER_*,
+    counts [B, ld] int32: a_k), on the device; a PQ_GERBER_BAD_INPUT date (fewer than 2 rows, a
+    non-finite value, a constant column, an asset that never moves beyond its threshold) has a NaN
+    block.  Does not synchronise."""
+    lib = _lib.load()
+    from .covariance import _gerber_check
+    threshold, variant = _gerber_check(threshold, variant)
+    B, tmax = int(rows.shape[0]), int(rows.shape[1])
+    n, dev = panel.n, panel.device
+    ld = round_up(n, 64)
+    if not 1 <= tmax <= _lib.PQ_GERBER_TMAX:
+        raise ValueError(f"gerber_cov: windows of up to {tmax} rows (supported: 1..{_lib.PQ_GERBER_TMAX})")
+    if out is None:
+        out = torch.zeros((B, ld, ld), dtype=F64, device=dev)
+    elif tuple(out.shape) != (B, ld, ld) or out.dtype != F64 or not out.is_contiguous():
+        raise ValueError(f"gerber_cov: out must be a contiguous float64 ({B}, {ld}, {ld}) tensor")
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    counts = torch.empty((B, ld), dtype=torch.int32, device=dev)
+    if B == 0:
+        return out, status, counts
+    rows = rows.contiguous()
+    per_date = ld * round_up(tmax, 64)   # bytes of a date's sign panel
+    per = max(1, min(B, int(chunk_bytes) // per_date))
+    St = torch.empty((per, per_date), dtype=torch.int8, device=dev)
+    for b0 in range(0, B, per):
+        b1 = min(B, b0 + per)
+        r, t = rows[b0:b1], tlen[b0:b1]
+        dg = panel.window_sumsq(r, t, panel.window_means(r, t))
+        _lib.check(lib.pq_gerber_cov_batched(_ptr(panel.R), panel.R.stride(0), n, _ptr(r), _ptr(t), tmax, b1 - b0,
+                                             _ptr(dg), dg.stride(0), threshold, variant, int(bool(corr)),
+                                             _lib.PQ_GERBER_SIGNS | _lib.PQ_GERBER_GRAM, _ptr(St),
+                                             _ptr(counts[b0:]), counts.stride(0), _ptr(out[b0:]), ld, out.stride(0),
+                                             _ptr(status[b0:]), _stream()), "pq_gerber_cov_batched")
+    return out, status, counts
 
 
 PCA_CHUNK_BYTES = 2 << 30   # Gram, eigenvector and work buffers of pca_window_form stay below this

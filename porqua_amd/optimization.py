@@ -145,7 +145,12 @@ class MeanVariance(Optimization):
     ``Covariance.estimate`` and ``objective_batch`` returns None, so a backtest runs the serial
     loop.  The QP window path on the factor form is deliberately not offered: its capacitance
     would be k + mg wide, and the backtest's group plan is built from the original row table,
-    which must not be mixed with the factor rows."""
+    which must not be mixed with the factor rows.
+
+    With the 'gerber' covariance, variant 2 (positive semi-definite by construction) takes the dense
+    batched route whatever ``prefer_lowrank`` says -- its thresholds are per date, so there is no
+    window form --; variant 1 can be indefinite, so ``objective_batch`` returns None and the serial
+    loop lets ``Covariance.estimate`` check and repair every date."""
 
     batch_handles_nan = True   # windows with gaps: pairwise covariance + skipna means, batched
 
@@ -167,21 +172,24 @@ class MeanVariance(Optimization):
         from . import engine
         if self.covariance.spec["method"] == "pca":   # the dense estimate, date by date
             return None
+        gerber = self.covariance.spec["method"] == "gerber"
+        if gerber and self.covariance.gerber_spec[1] != 2:   # variant 1 can be indefinite: the checked serial loop
+            return None
         nan = stage.panel.has_nan   # missing values: pairwise covariance, dense P (no window form)
-        lowrank = stage.prefer_lowrank and self.covariance.spec["method"] != "duv" and not nan
+        lowrank = stage.prefer_lowrank and self.covariance.spec["method"] != "duv" and not nan and not gerber
         S, pdiag, mu_c, dg = self.covariance.estimate_batch_lr(
             stage.panel, stage.rows, stage.tlen, out=None if lowrank else stage.P_buffer(),
-            plan=None if (nan or lowrank) else stage.slide_plan(), materialise=not lowrank,
+            plan=None if (nan or lowrank or gerber) else stage.slide_plan(), materialise=not lowrank,
             groups=stage.group_plan() if lowrank else None)
         ra = float(self.params["risk_aversion"])
         B = stage.batch
         dev = stage.device
-        if nan and S is None:
+        if (nan or gerber) and S is None:
             return None
         # 'ledoit_wolf' / 'oas': Sigma* = (1 - delta) S + pdiag I with a per-date delta; the
         # factor (1 - delta) goes into w_scale (window form) or the returned scale (dense)
         delta = getattr(self.covariance, "shrinkage_batch_", None)
-        if mu_c is None and not nan:  # duv: identity covariance
+        if mu_c is None and not nan and not gerber:  # duv: identity covariance
             S = stage.identity_P()
             pdiag = torch.zeros(B, dtype=torch.float64, device=dev)
         elif lowrank:   # factored form S = Xc'Xc / (T - 1) for the Woodbury solver (no n x n S)
@@ -620,7 +628,8 @@ class RiskParity(Optimization):
     the uncentred form (1, sigma2) of the k factor rows of engine.pca_window_form, built once per
     ``solve_windows``; the per-date factor counts and noise levels stay in the covariance's
     ``n_factors_batch_`` / ``noise_variance_batch_``, and a date whose factor model is bad input
-    (sigma2 NaN) is PQ_RP_BAD_INPUT.
+    (sigma2 NaN) is PQ_RP_BAD_INPUT.  'gerber' is not served (NotImplementedError): the kernel
+    needs a window form, and the Gerber thresholds are per date, so no rows are shared.
 
     ``risk_budget``: a dict or Series over the assets (None: equal budgets); an asset of the
     date's selection without an entry is an error, entries must be > 0, and the budgets are
@@ -749,7 +758,9 @@ class HierarchicalRiskParity(Optimization):
     'linear_shrinkage', 'ledoit_wolf' / 'oas' (the intensity of engine.shrinkage_intensity), 'duv'
     -- the (a, c) mapping of RiskParity (covariance_window_form), as Sigma = alpha S + c I on the
     sample covariance S; 'pca': S the Gram Z'Z of the k factor rows of engine.pca_window_form with
-    alpha = 1 and c = sigma2 (a date whose factor model is bad input is PQ_HRP_BAD_INPUT).
+    alpha = 1 and c = sigma2 (a date whose factor model is bad input is PQ_HRP_BAD_INPUT); 'gerber':
+    S the dense estimate of engine.gerber_cov per chunk of dates, alpha = 1 and c = 0 (a bad-input
+    date arrives as NaN and is PQ_HRP_BAD_INPUT by the kernel's own check).
     ``linkage``: 'single' (Lopez de Prado's choice, the default), 'complete',
     'average' or 'weighted', with SciPy's meaning; any other name raises NotImplementedError --
     'ward' too, though the kernel has it: engine.hrp_weights(method='ward') reaches it --, and
@@ -791,6 +802,13 @@ class HierarchicalRiskParity(Optimization):
             pf = self.covariance.window_form_pca(panel, rows, tlen)
             return engine.hrp_weights(pf.panel, pf.rows, pf.tlen, alpha=1.0, c=pf.sigma2, centred=False,
                                       scale=self.budget_scale(), linkage=linkage, method=self.linkage)
+        if self.covariance.spec["method"] == "gerber":   # the dense Gerber estimate in place of Panel.cov
+            threshold, variant = self.covariance.gerber_spec
+
+            def dense(r, t, out):
+                return engine.gerber_cov(panel, r, t, threshold=threshold, variant=variant, out=out)[0]
+            return engine.hrp_weights(panel, rows, tlen, alpha=1.0, c=0.0, scale=self.budget_scale(),
+                                      linkage=linkage, method=self.linkage, dense=dense)
         mu = panel.window_means(rows, tlen)
         dg = panel.window_sumsq(rows, tlen, mu)
         a, c = covariance_window_form(self.covariance, panel, rows, tlen, dg)
