@@ -808,6 +808,51 @@ int pq_gerber_cov_batched(const double* panel, int64_t ldp, int32_t n, const int
                           int32_t variant, int32_t corr, int32_t stages, int8_t* St, int32_t* counts, int64_t ldc,
                           double* out, int32_t ld, int64_t out_stride, int32_t* status, void* stream);
 
+/* Rank covariance of every date: Spearman's rho or Kendall's tau-b of the window's columns, scaled
+ * by the window's own standard deviations.  X is date b's T x n window, read exactly as
+ * pq_cov_batched reads it, dg (batch x dg_stride) its diag(Xc'Xc) as pq_window_sumsq leaves it:
+ *   d_tk = 2 #{u : x_uk < x_tk} + #{u : x_uk == x_tk} + 1   (the doubled mid-rank, IEEE < and ==),
+ *   c_tk = d_tk - (T + 1);
+ *   Spearman: C = c'c, g_ij = C_ij / sqrt(C_ii C_jj);
+ *   Kendall:  kappa_(s,t),k = sgn(x_tk - x_sk) for every pair of days s < t, H = kappa'kappa,
+ *             g_ij = H_ij / sqrt(H_ii H_jj)   (tau-b; H_kk the number of pairs not tied in k);
+ *   sd_k = sqrt(dg_k / (T - 1));  out_ij = g_ij (sd_i sd_j) (PQ_RANK_COV), g_ij (PQ_RANK_CORR) or
+ *   the integer C_ij / H_ij as an exact double (PQ_RANK_COUNTS).  C and H are exact integers.
+ * stages & PQ_RANK_RANKS: the ranking kernel (per 16 assets and date) writes status, the exact
+ * diagonal C_kk or H_kk into diag (batch x ldd doubles, zeros in [n, ldd)), and the ranks into
+ * scratch -- Kendall: int16 d, asset-major, batch x round_up(n, 64) x round_up(tmax, 64) (16-byte
+ * aligned, zeros past the window and past n; ldr unused); Spearman: c as doubles, batch x tmax rows
+ * of pitch ldr >= n (zero rows past the window), the panel whose Gram per date (pq_cov_batched,
+ * mode 1, rows b tmax + t) is C.
+ * stages & PQ_RANK_FINISH: Kendall: the Gram kernel (per pair of 64-asset blocks I <= J and date)
+ * builds the sign fragments of the T (T - 1) / 2 day pairs from the two rank strips in LDS, forms H
+ * with v_mfma_i32_16x16x64_i8 and writes the tile and its transpose; the pair panel never exists
+ * in memory.  Spearman: out must hold C (as pq_cov_batched left it), and the epilogue is applied
+ * in place.  stages = 3 runs both and is for Kendall only: Spearman's Gram has to come between
+ * its two stages, and stages = 3 with PQ_RANK_SPEARMAN is an error.
+ * out is batch x ld x ld (date stride out_stride), ld a multiple of 64; [0, n) x [0, n) of a date
+ * carries the result, symmetric bit for bit, and the rows and columns [n, round_up(n, 64)) are set
+ * to zero.  status[b]: PQ_RANK_OK, or PQ_RANK_BAD_INPUT -- T < 2, a non-finite value, a constant
+ * column (C_kk = H_kk = 0) --, for which the date's n x n block is NaN; nothing faults and no date
+ * affects another.  Integer LDS atomics only: the same input gives the same bits.
+ * 1 <= tmax <= PQ_RANK_TMAX, n >= 1, ldp, dg_stride, ldd >= n.  The call does not synchronise; only
+ * host-checkable arguments (null pointers, the sizes, an unknown kind or mode, stages outside
+ * 1..3 or 3 for Spearman) return an error, and then nothing is launched. */
+#define PQ_RANK_OK 0
+#define PQ_RANK_BAD_INPUT 1
+#define PQ_RANK_SPEARMAN 0
+#define PQ_RANK_KENDALL 1
+#define PQ_RANK_COV 0
+#define PQ_RANK_CORR 1
+#define PQ_RANK_COUNTS 2
+#define PQ_RANK_RANKS 1
+#define PQ_RANK_FINISH 2
+#define PQ_RANK_TMAX 512
+int pq_rank_cov_batched(const double* panel, int64_t ldp, int32_t n, const int32_t* rows, const int32_t* tlen,
+                        int32_t tmax, int32_t batch, const double* dg, int64_t dg_stride, int32_t kind, int32_t mode,
+                        int32_t stages, void* scratch, int64_t ldr, double* diag, int64_t ldd, double* out,
+                        int32_t ld, int64_t out_stride, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

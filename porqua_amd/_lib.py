@@ -53,6 +53,13 @@ PQ_GERBER_OK, PQ_GERBER_BAD_INPUT = range(2)
 PQ_GERBER_TMAX = 1024
 PQ_GERBER_SIGNS, PQ_GERBER_GRAM = 1, 2
 
+# pq_rank_cov_batched: per-date status, the estimator, the output mode, the stages and the longest window
+PQ_RANK_OK, PQ_RANK_BAD_INPUT = range(2)
+PQ_RANK_SPEARMAN, PQ_RANK_KENDALL = range(2)
+PQ_RANK_COV, PQ_RANK_CORR, PQ_RANK_COUNTS = range(3)
+PQ_RANK_RANKS, PQ_RANK_FINISH = 1, 2
+PQ_RANK_TMAX = 512
+
 PQ_PG_RECORD = 384                  # doubles per problem of the grouped polish record
 PQ_PG_PASS_SCRATCH = 123537          # doubles per slide group of the split polish window passes
 PQ_PG_PENDING, PQ_PG_DONE, PQ_PG_FALLBACK, PQ_PG_SKIP = range(4)
@@ -269,6 +276,8 @@ _EXPORTS = {
     "pq_gerber_cov_batched": ([c_dp, c_int64, c_int32, c_dp, c_dp, c_int32, c_int32, c_dp, c_int64,
                                ctypes.c_double, c_int32, c_int32, c_int32, c_dp, c_dp, c_int64, c_dp, c_int32,
                                c_int64, c_dp, c_dp], c_int32),
+    "pq_rank_cov_batched": ([c_dp, c_int64, c_int32, c_dp, c_dp, c_int32, c_int32, c_dp, c_int64, c_int32, c_int32,
+                             c_int32, c_dp, c_int64, c_dp, c_int64, c_dp, c_int32, c_int64, c_dp, c_dp], c_int32),
 }
 
 _lib = None

@@ -17,7 +17,9 @@ of the window kept, the rest of the spectrum replaced by one trace-preserving no
 (engine.pca_window_form), and 'gerber' is the Gerber statistic (Gerber et al. 2022; Riskfolio-Lib's
 gerber1 / gerber2): co-movement counts of the raw returns beyond ``threshold`` window standard
 deviations in place of the second moments (engine.gerber_cov; spec ``threshold`` 0.5 and
-``variant`` 2 by default).  ``estimate_batch`` is the batched backtest entry: all
+``variant`` 2 by default), and 'spearman' / 'kendall' are the rank correlations -- Spearman's rho
+and Kendall's tau-b of the window's columns, with mid-ranks for ties -- scaled by the window's
+standard deviations (engine.rank_cov).  ``estimate_batch`` is the batched backtest entry: all
 rebalance dates of a device-resident panel at once, results left on the device.
 """
 from __future__ import annotations
@@ -49,6 +51,11 @@ def _shrink_lambda(lam):
 
 # data-driven shrinkage towards mean(diag S) I: Sigma* = (1 - delta) S + delta mean(diag S) I
 SHRINKAGE_METHODS = ("ledoit_wolf", "oas")
+# rank correlations scaled by the window's standard deviations (engine.rank_cov)
+RANK_METHODS = ("spearman", "kendall")
+# methods estimated per date from the date's own window, as a dense matrix only: no window form
+# that dates could share (estimate_batch_lr serves them with materialise=True only)
+DENSE_ONLY_METHODS = ("gerber",) + RANK_METHODS
 
 
 class Covariance:
@@ -68,7 +75,13 @@ class Covariance:
     anything else raises ValueError before the device is touched): the dense estimate of
     engine.gerber_cov.  Its thresholds are the window's own standard deviations, so there is no
     window form shared between dates: ``estimate_batch_lr`` serves it with ``materialise=True``
-    only.  Variant 2 is positive semi-definite by construction, variant 1 can be indefinite."""
+    only.  Variant 2 is positive semi-definite by construction, variant 1 can be indefinite.
+
+    methods 'spearman' and 'kendall' (no parameters): the dense estimate of engine.rank_cov, for
+    complete windows.  Both are positive semi-definite by construction, and Kendall's tau-b is
+    positive definite on typical windows with more assets than rows, where Spearman's rho (like the
+    sample covariance) is singular.  The ranks belong to each date's own window, so
+    ``estimate_batch_lr`` serves them with ``materialise=True`` only."""
 
     def __init__(self, spec: CovarianceSpecification = None, *args, **kwargs):
         self.spec = CovarianceSpecification(*args, **kwargs) if spec is None else spec
@@ -98,6 +111,8 @@ class Covariance:
             covmat, self.n_factors_, self.noise_variance_ = _cov_pca(X, self.n_factors)
         elif method == "gerber":
             covmat = cov_gerber(X, *self.gerber_spec)
+        elif method in RANK_METHODS:
+            covmat = _cov_rank(X, method)
         else:
             raise NotImplementedError("This method is not implemented yet")
         if self.spec.get("check_positive_definite") and not isPD(covmat):
@@ -170,6 +185,16 @@ class Covariance:
                 out[:, n:, :] = 0.0
                 out[:, :n, n:] = 0.0
             S, _, _ = engine.gerber_cov(panel, rows, tlen, threshold=threshold, variant=variant, out=out)
+            return S, torch.zeros(int(rows.shape[0]), dtype=torch.float64, device=S.device), None, None
+        if method in RANK_METHODS:
+            if not materialise:
+                raise NotImplementedError(f"the {method!r} covariance has no window form: the ranks belong to each "
+                                          "date's own window, so no rows are shared between dates; estimate the "
+                                          "dense matrix (materialise=True)")
+            if panel.has_nan:   # complete windows only: the serial loop reports it
+                return None, None, None, None
+            from . import engine
+            S, _, _ = engine.rank_cov(panel, rows, tlen, kind=method, out=out)   # (it zeroes the padding)
             return S, torch.zeros(int(rows.shape[0]), dtype=torch.float64, device=S.device), None, None
         if method not in ("pearson", "linear_shrinkage") + SHRINKAGE_METHODS:
             raise NotImplementedError("This method is not implemented yet")
@@ -347,6 +372,41 @@ def cov_gerber(X, threshold=0.5, variant=2):
     if isinstance(X, pd.DataFrame):
         S = pd.DataFrame(S, index=X.columns, columns=X.columns)
     return S
+
+
+def _cov_rank(X, kind):
+    """engine.rank_cov at batch 1 on one complete window; ValueError for missing values or bad input."""
+    from . import _lib, engine
+    Xv = np.ascontiguousarray(X.to_numpy() if hasattr(X, "to_numpy") else X, dtype=np.float64)
+    if np.isnan(Xv).any():
+        raise ValueError(f"the {kind} covariance needs complete windows")
+    T, n = Xv.shape
+    if not 1 <= T <= _lib.PQ_RANK_TMAX:
+        raise ValueError(f"the {kind} covariance: bad input ({T} rows, supported: 2..{_lib.PQ_RANK_TMAX})")
+    pan = engine.Panel(Xv)
+    rows, tlen = pan.rows_to_device(np.arange(T, dtype=np.int32)[None], np.array([T], dtype=np.int32))
+    S, status, _ = engine.rank_cov(pan, rows, tlen, kind=kind)
+    if int(status[0].item()) != _lib.PQ_RANK_OK:
+        raise ValueError(f"the {kind} covariance: bad input (fewer than 2 rows, non-finite data or a constant column)")
+    S = S[0, :n, :n].cpu().numpy()
+    if isinstance(X, pd.DataFrame):
+        S = pd.DataFrame(S, index=X.columns, columns=X.columns)
+    return S
+
+
+def cov_spearman(X):
+    """Spearman rank covariance of one complete window: Spearman's rho of the columns (mid-ranks
+    for ties) times the outer product of the window's standard deviations.  Positive
+    semi-definite.  ValueError for missing values or a bad-input window."""
+    return _cov_rank(X, "spearman")
+
+
+def cov_kendall(X):
+    """Kendall rank covariance of one complete window: Kendall's tau-b of the columns times the
+    outer product of the window's standard deviations.  Positive semi-definite, and positive
+    definite on typical windows with more assets than rows.  ValueError for missing values or a
+    bad-input window."""
+    return _cov_rank(X, "kendall")
 
 
 def cov_ledoit_wolf(X):

@@ -2140,6 +2140,79 @@ def gerber_cov(panel: "Panel", rows, tlen, threshold: float = 0.5, variant: int 
     return out, status, counts
 
 
+RANK_CHUNK_BYTES = 2 << 30   # the rank scratch of rank_cov stays below this
+RANK_KINDS = {"spearman": _lib.PQ_RANK_SPEARMAN, "kendall": _lib.PQ_RANK_KENDALL}
+RANK_OUTPUTS = {"cov": _lib.PQ_RANK_COV, "corr": _lib.PQ_RANK_CORR, "counts": _lib.PQ_RANK_COUNTS}
+
+
+def rank_cov(panel: "Panel", rows, tlen, kind: str = "spearman", output: str = "cov", out=None,
+             chunk_bytes: int = RANK_CHUNK_BYTES):
+    """The rank covariance of every window (pq_rank_cov_batched): Spearman's rho (``kind``
+    'spearman') or Kendall's tau-b ('kendall') of the window's columns as the correlation g, and
+    Sigma_ij = g_ij sd_i sd_j with the window's own standard deviations (``output`` 'cov'); 'corr':
+    g itself; 'counts': the exact integer numerator as doubles -- C = c'c of the centred doubled
+    mid-ranks (Spearman), H = concordant minus discordant pairs of days (Kendall).  Spearman: the
+    ranking kernel writes the rank panel, Panel.cov(mode=1) forms its Gram per date on the FP64
+    matrix cores, an epilogue kernel finishes in place; Kendall: the ranking kernel writes int16
+    ranks and the Gram kernel builds the signs of the T (T - 1) / 2 day pairs on the fly for the
+    int8 matrix cores.  ``rows`` / ``tlen``: the device row table, at most _lib.PQ_RANK_TMAX rows
+    per window.  ``out``: a (B, ld, ld) buffer, ld = round_up(n, 64): [0, n) x [0, n) of every date
+    carries the result and the padding is set to zero (None: a buffer is allocated).  The rank
+    panels are scratch, allocated per chunk of dates so that they stay under ``chunk_bytes``; the
+    results do not depend on the chunking.  Returns (S [B, ld, ld], status [B] int32:
+    _lib.PQ_RANK_*, diag [B, ld] float64: C_kk or H_kk, exact), on the device; a PQ_RANK_BAD_INPUT
+    date (fewer than 2 rows, a non-finite value, a constant column) has a NaN block.  ValueError
+    for an unknown kind or output, a wrong ``out`` or a window length outside 1.._lib.PQ_RANK_TMAX,
+    before anything runs.  Does not synchronise."""
+    lib = _lib.load()
+    if kind not in RANK_KINDS:
+        raise ValueError(f"rank_cov: kind = {kind!r} is not one of {sorted(RANK_KINDS)}")
+    if output not in RANK_OUTPUTS:
+        raise ValueError(f"rank_cov: output = {output!r} is not one of {sorted(RANK_OUTPUTS)}")
+    B, tmax = int(rows.shape[0]), int(rows.shape[1])
+    n, dev = panel.n, panel.device
+    ld = round_up(n, 64)
+    if not 1 <= tmax <= _lib.PQ_RANK_TMAX:
+        raise ValueError(f"rank_cov: windows of up to {tmax} rows (supported: 1..{_lib.PQ_RANK_TMAX})")
+    if out is None:
+        out = torch.empty((B, ld, ld), dtype=F64, device=dev)
+    elif tuple(out.shape) != (B, ld, ld) or out.dtype != F64 or not out.is_contiguous():
+        raise ValueError(f"rank_cov: out must be a contiguous float64 ({B}, {ld}, {ld}) tensor")
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    diag = torch.empty((B, ld), dtype=F64, device=dev)
+    if B == 0:
+        return out, status, diag
+    rows = rows.contiguous()
+    kd, mode = RANK_KINDS[kind], RANK_OUTPUTS[output]
+    spearman = kd == _lib.PQ_RANK_SPEARMAN
+    per_date = 8 * tmax * n if spearman else 2 * ld * round_up(tmax, 64)   # bytes of a date's rank panel
+    per = max(1, min(B, int(chunk_bytes) // per_date))
+    if spearman:   # date b of a chunk is the rows [b tmax, (b + 1) tmax) of the scratch panel
+        scratch = torch.empty((per * tmax, n), dtype=F64, device=dev)
+        ranks = Panel(scratch, device=dev)
+        rrows = torch.arange(per * tmax, dtype=torch.int32, device=dev).view(per, tmax)
+        rlen = torch.full((per,), tmax, dtype=torch.int32, device=dev)   # the rows past a window are zero
+    else:
+        scratch = torch.empty((per, per_date // 2), dtype=torch.int16, device=dev)
+
+    def call(b0, b1, r, t, dg, stages):
+        _lib.check(lib.pq_rank_cov_batched(_ptr(panel.R), panel.R.stride(0), n, _ptr(r), _ptr(t), tmax, b1 - b0,
+                                           _ptr(dg), dg.stride(0), kd, mode, stages, _ptr(scratch), n,
+                                           _ptr(diag[b0:]), diag.stride(0), _ptr(out[b0:]), ld, out.stride(0),
+                                           _ptr(status[b0:]), _stream()), "pq_rank_cov_batched")
+    for b0 in range(0, B, per):
+        b1 = min(B, b0 + per)
+        r, t = rows[b0:b1], tlen[b0:b1]
+        dg = panel.window_sumsq(r, t, panel.window_means(r, t))
+        if spearman:
+            call(b0, b1, r, t, dg, _lib.PQ_RANK_RANKS)
+            ranks.cov(rrows[:b1 - b0], rlen[:b1 - b0], mode=1, out=out[b0:b1])
+            call(b0, b1, r, t, dg, _lib.PQ_RANK_FINISH)
+        else:
+            call(b0, b1, r, t, dg, _lib.PQ_RANK_RANKS | _lib.PQ_RANK_FINISH)
+    return out, status, diag
+
+
 PCA_CHUNK_BYTES = 2 << 30   # Gram, eigenvector and work buffers of pca_window_form stay below this
 # the eigensolver of pca_window_form where the caller names none: on the 4749 window Grams of config 3
 # (252 x 252) rocSOLVER's eigh takes 432 ms, the block-Jacobi kernels 2994 ms (profiles/pca_cov_bench.log)

@@ -35,7 +35,7 @@ import pandas as pd
 
 from . import qp_problems
 from .constraints import Constraints
-from .covariance import Covariance
+from .covariance import DENSE_ONLY_METHODS, RANK_METHODS, Covariance
 from .helper_functions import to_numpy
 from .mean_estimation import MeanEstimator
 from .optimization_data import OptimizationData
@@ -150,7 +150,9 @@ class MeanVariance(Optimization):
     With the 'gerber' covariance, variant 2 (positive semi-definite by construction) takes the dense
     batched route whatever ``prefer_lowrank`` says -- its thresholds are per date, so there is no
     window form --; variant 1 can be indefinite, so ``objective_batch`` returns None and the serial
-    loop lets ``Covariance.estimate`` check and repair every date."""
+    loop lets ``Covariance.estimate`` check and repair every date.  'spearman' and 'kendall' are
+    positive semi-definite by construction and take the dense batched route in the same way
+    (covariance.DENSE_ONLY_METHODS names the methods without a window form)."""
 
     batch_handles_nan = True   # windows with gaps: pairwise covariance + skipna means, batched
 
@@ -172,24 +174,25 @@ class MeanVariance(Optimization):
         from . import engine
         if self.covariance.spec["method"] == "pca":   # the dense estimate, date by date
             return None
-        gerber = self.covariance.spec["method"] == "gerber"
-        if gerber and self.covariance.gerber_spec[1] != 2:   # variant 1 can be indefinite: the checked serial loop
+        method = self.covariance.spec["method"]
+        dense_only = method in DENSE_ONLY_METHODS   # estimated per date from its own window: no window form
+        if method == "gerber" and self.covariance.gerber_spec[1] != 2:   # variant 1 can be indefinite: the checked serial loop
             return None
         nan = stage.panel.has_nan   # missing values: pairwise covariance, dense P (no window form)
-        lowrank = stage.prefer_lowrank and self.covariance.spec["method"] != "duv" and not nan and not gerber
+        lowrank = stage.prefer_lowrank and method != "duv" and not nan and not dense_only
         S, pdiag, mu_c, dg = self.covariance.estimate_batch_lr(
             stage.panel, stage.rows, stage.tlen, out=None if lowrank else stage.P_buffer(),
-            plan=None if (nan or lowrank or gerber) else stage.slide_plan(), materialise=not lowrank,
+            plan=None if (nan or lowrank or dense_only) else stage.slide_plan(), materialise=not lowrank,
             groups=stage.group_plan() if lowrank else None)
         ra = float(self.params["risk_aversion"])
         B = stage.batch
         dev = stage.device
-        if (nan or gerber) and S is None:
+        if (nan or dense_only) and S is None:
             return None
         # 'ledoit_wolf' / 'oas': Sigma* = (1 - delta) S + pdiag I with a per-date delta; the
         # factor (1 - delta) goes into w_scale (window form) or the returned scale (dense)
         delta = getattr(self.covariance, "shrinkage_batch_", None)
-        if mu_c is None and not nan and not gerber:  # duv: identity covariance
+        if mu_c is None and not nan and not dense_only:  # duv: identity covariance
             S = stage.identity_P()
             pdiag = torch.zeros(B, dtype=torch.float64, device=dev)
         elif lowrank:   # factored form S = Xc'Xc / (T - 1) for the Woodbury solver (no n x n S)
@@ -629,7 +632,8 @@ class RiskParity(Optimization):
     ``solve_windows``; the per-date factor counts and noise levels stay in the covariance's
     ``n_factors_batch_`` / ``noise_variance_batch_``, and a date whose factor model is bad input
     (sigma2 NaN) is PQ_RP_BAD_INPUT.  'gerber' is not served (NotImplementedError): the kernel
-    needs a window form, and the Gerber thresholds are per date, so no rows are shared.
+    needs a window form, and the Gerber thresholds are per date, so no rows are shared; nor are
+    'spearman' and 'kendall' (NotImplementedError): the ranks belong to each date's own window.
 
     ``risk_budget``: a dict or Series over the assets (None: equal budgets); an asset of the
     date's selection without an entry is an error, entries must be > 0, and the budgets are
@@ -760,7 +764,8 @@ class HierarchicalRiskParity(Optimization):
     sample covariance S; 'pca': S the Gram Z'Z of the k factor rows of engine.pca_window_form with
     alpha = 1 and c = sigma2 (a date whose factor model is bad input is PQ_HRP_BAD_INPUT); 'gerber':
     S the dense estimate of engine.gerber_cov per chunk of dates, alpha = 1 and c = 0 (a bad-input
-    date arrives as NaN and is PQ_HRP_BAD_INPUT by the kernel's own check).
+    date arrives as NaN and is PQ_HRP_BAD_INPUT by the kernel's own check); 'spearman' / 'kendall':
+    the dense estimate of engine.rank_cov in the same way.
     ``linkage``: 'single' (Lopez de Prado's choice, the default), 'complete',
     'average' or 'weighted', with SciPy's meaning; any other name raises NotImplementedError --
     'ward' too, though the kernel has it: engine.hrp_weights(method='ward') reaches it --, and
@@ -807,6 +812,13 @@ class HierarchicalRiskParity(Optimization):
 
             def dense(r, t, out):
                 return engine.gerber_cov(panel, r, t, threshold=threshold, variant=variant, out=out)[0]
+            return engine.hrp_weights(panel, rows, tlen, alpha=1.0, c=0.0, scale=self.budget_scale(),
+                                      linkage=linkage, method=self.linkage, dense=dense)
+        if self.covariance.spec["method"] in RANK_METHODS:   # the dense rank estimate in place of Panel.cov
+            kind = self.covariance.spec["method"]
+
+            def dense(r, t, out):
+                return engine.rank_cov(panel, r, t, kind=kind, out=out)[0]
             return engine.hrp_weights(panel, rows, tlen, alpha=1.0, c=0.0, scale=self.budget_scale(),
                                       linkage=linkage, method=self.linkage, dense=dense)
         mu = panel.window_means(rows, tlen)
