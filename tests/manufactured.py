@@ -40,7 +40,17 @@ admm_reference.admm_woodbury_f64 for the ADMM tests.
 
 ``family`` builds the four families of batches (A: centred, box [0, 1], budget; B: centred, box
 [0, 0.05], weights at the upper bound; C: budget + 10 sector caps; W: uncentred, box [-1, 1])
-on consecutive daily windows of the synthetic factor panel.
+on consecutive daily windows of the synthetic factor panel.  With (n, t, sizes, ridge) it builds
+the same families at other shapes, and three more: R16 / R32 (40 disjoint groups next to the
+budget, 16 / 32 of them active: 17 / 33 active rows that stay independent of the budget because
+some group is always inactive), N (box only, no general row) and U (no box).
+
+For the per-date kernels, which tests/test_polish_per_date_gpu.py calls directly: ``start_state``
+is a synthetic starting point (x* with x_F moved by 1e-7, multipliers and row values from which
+polish_rules.h's start_box / start_row, restated in ``rule_start_box`` / ``rule_start_row``, return
+exactly the constructed classification; ``flip``: one variable wrongly classified),
+``reduced_kkt_woodbury_f64`` the yardstick of k_polish_w's Woodbury mode, ``PER_DATE`` the batches
+and ``per_date_model`` the yardstick of each batch's mode.
 """
 from __future__ import annotations
 
@@ -56,7 +66,7 @@ N, T = 300, 120
 # ridge = RIDGE[family] x mean diag P of the batch's ridged dates.  0.05 where only the parity bars apply (W);
 # the families whose dates meet the tight bar of tests/test_polish_buckets_gpu.py take the ridge at which
 # stop_rule_bound stays under 1e-10 for every date (tests/test_manufactured.py)
-RIDGE = {"A": 4.0, "B": 1.0, "C": 1.0, "W": 0.05}
+RIDGE = {"A": 4.0, "B": 1.0, "C": 1.0, "W": 0.05, "R": 4.0, "N": 4.0, "U": 4.0}
 SEED = 20250711
 
 
@@ -124,6 +134,13 @@ def manufacture(P, lb, ub, C, lg, ug, x0, side, act, rng, p_diag=0.0, norm_width
     M[:k, k:] = Cl[act][:, F].T
     M[k:, :k] = Cl[act][:, F]
     rhs = np.concatenate([-q[F].astype(LD) - P[np.ix_(F, B)] @ x[B], d_a - Cl[act][:, B] @ x[B]])
+    if k == 0:
+        # every variable at a bound: the active rows have no free support, their multipliers are not
+        # determined and stay as drawn (the kernels leave them at the starting point's); z = -g of them
+        g = P @ x + q.astype(LD) + Cl.T @ lam
+        zsign = np.where(side == 1, -1.0, 1.0) * -g
+        return Optimum(F=F, side=side.copy(), act=act, q=q, p_diag=float(p_diag), x=x, lam=lam, z=-g, s=s,
+                       margins=dict(z_min_rel=float(zsign.min() / s), moved=0.0, kkt_res=0.0))
     sol = _solve_ld(M, rhs)
     moved = float(np.abs(sol[:k] - x[F]).max() / np.abs(x).max())
     x[F] = sol[:k]
@@ -166,8 +183,11 @@ ROW_ZERO = 1e-14      # ... with a row residual within ROW_ZERO (1 + |d_a| + |C_
 # (the kernels' copies: POLISH_STOP_REL, POLISH_ROW_ZERO in porqua_amd/csrc/polish_rules.h)
 
 
-def reduced_kkt_f64(X, mu, psw, p_diag, q, C, lg, ug, lb, ub, side, act, x0, lam0, delta, refine, stop=None):
+def reduced_kkt_f64(X, mu, psw, p_diag, q, C, lg, ug, lb, ub, side, act, x0, lam0, delta, refine, stop=None,
+                    P=None):
     """The float64 yardstick (module docstring): returns (x, lam, z_box, steps), of length n / mg / n.
+    ``P`` (float64, n x n; X, mu, psw and p_diag are then unused): the dense form of polish.hip, P_FF, P_FB x_B
+    and the final gradient taken from the matrix itself.
     ``side`` 0 / 1 / 2 per variable, ``act`` bool per row, (x0, lam0) the starting point
     (the ADMM point), ``delta`` absolute.  ``stop`` (absolute; None: every step is taken): the
     stop rule every polish kernel applies before a step (polish.hip, polish_w.hip, k_pg_solve,
@@ -177,13 +197,17 @@ def reduced_kkt_f64(X, mu, psw, p_diag, q, C, lg, ug, lb, ub, side, act, x0, lam
     cond(P_FF) u where the kernels, by design, stop at ~ stop / lambda_min(P_FF)."""
     n = len(q)
     C = np.asarray(C, dtype=np.float64).reshape(-1, n)
-    Xc = X if mu is None else X - mu
     F, B = np.flatnonzero(side == 0), np.flatnonzero(side != 0)
     k, ma = len(F), int(np.sum(act))
-    xb = np.where(side == 1, lb, np.where(side == 2, ub, 0.0))
-    Xf = Xc[:, F]
-    Pff = psw * (Xf.T @ Xf) + p_diag * np.eye(k)
-    rF = -q[F] - psw * (Xf.T @ (Xc[:, B] @ xb[B]))
+    xb = np.where(side == 1, lb, np.where(side == 2, ub, 0.0)) if lb is not None else np.zeros(n)
+    if P is None:
+        Xc = X if mu is None else X - mu
+        Xf = Xc[:, F]
+        Pff = psw * (Xf.T @ Xf) + p_diag * np.eye(k)
+        rF = -q[F] - psw * (Xf.T @ (Xc[:, B] @ xb[B]))
+    else:
+        Pff = P[np.ix_(F, F)]
+        rF = -q[F] - P[np.ix_(F, B)] @ xb[B]
     Ca = C[act]
     dA = np.where(np.isfinite(ug), ug, lg)[act] - Ca[:, B] @ xb[B]
     M = np.zeros((k + ma, k + ma))
@@ -209,6 +233,56 @@ def reduced_kkt_f64(X, mu, psw, p_diag, q, C, lg, ug, lb, ub, side, act, x0, lam
     x[F] = sol[:k]
     lam = np.zeros(C.shape[0])
     lam[act] = sol[k:]
+    g = (psw * (Xc.T @ (Xc @ x)) + p_diag * x if P is None else P @ x) + q + C.T @ lam
+    zb = np.where(side != 0, -g, 0.0)
+    return x, lam, zb, steps
+
+
+def reduced_kkt_woodbury_f64(X, mu, psw, p_diag, q, C, lg, ug, lb, ub, side, act, x0, lam0, delta, refine, stop=None):
+    """The float64 yardstick of k_polish_w's Woodbury mode (free set beyond the compact scratch), same
+    arguments and return as reduced_kkt_f64.  It restates that mode's algebra, not its summation order:
+    A = P_FF + delta I = psw X_F'X_F + dl I (dl = p_diag + delta) is never formed but applied as
+
+        A^-1 v = (v - X_F' Cm^-1 X_F v) / dl,    Cm = (dl / psw) I + X_F X_F'   (T x T, Cholesky),
+
+    Z = A^-1 C_aF', S = C_aF Z + delta I, and a step of the refinement is t = A^-1 r_F,
+    dlam = S^-1 (C_aF t - r_a), dx = t - Z dlam, with the exact residuals (r_F, r_a) of the unregularised
+    system.  As the kernel does it takes max(refine, 2) steps at most and applies the stop rule before each."""
+    n = len(q)
+    C = np.asarray(C, dtype=np.float64).reshape(-1, n)
+    Xc = X if mu is None else X - mu
+    F, B = np.flatnonzero(side == 0), np.flatnonzero(side != 0)
+    k, ma, T = len(F), int(np.sum(act)), X.shape[0]
+    xb = np.where(side == 1, lb, np.where(side == 2, ub, 0.0))
+    Xf = Xc[:, F]
+    dl = p_diag + delta
+    cm = sla.cho_factor((dl / psw) * np.eye(T) + Xf @ Xf.T, lower=True)
+    ainv = lambda v: (v - Xf.T @ sla.cho_solve(cm, Xf @ v)) / dl
+    rF = -q[F] - psw * (Xf.T @ (Xc[:, B] @ xb[B]))
+    Ca = C[act]
+    CaF = Ca[:, F]
+    dA = np.where(np.isfinite(ug), ug, lg)[act] - Ca[:, B] @ xb[B]
+    Z = ainv(CaF.T) if ma else np.zeros((k, 0))
+    S = sla.cho_factor(CaF @ Z + delta * np.eye(ma), lower=True) if ma else None
+    xF, lam_a = x0[F].copy(), lam0[act].copy()
+    steps = 0
+    for _ in range(max(refine, 2)):
+        r = rF - psw * (Xf.T @ (Xf @ xF)) - p_diag * xF - CaF.T @ lam_a
+        ra = dA - CaF @ xF
+        ra[np.abs(ra) <= ROW_ZERO * (1.0 + np.abs(dA) + np.abs(CaF @ xF))] = 0.0
+        if stop is not None and max(np.abs(r).max(initial=0.0), np.abs(ra).max(initial=0.0)) <= stop:
+            break
+        t = ainv(r)
+        if ma:
+            dlam = sla.cho_solve(S, CaF @ t - ra)
+            t = t - Z @ dlam
+            lam_a = lam_a + dlam
+        xF = xF + t
+        steps += 1
+    x = xb.copy()
+    x[F] = xF
+    lam = np.zeros(C.shape[0])
+    lam[act] = lam_a
     g = psw * (Xc.T @ (Xc @ x)) + p_diag * x + q + C.T @ lam
     zb = np.where(side != 0, -g, 0.0)
     return x, lam, zb, steps
@@ -305,10 +379,23 @@ class Batch:
     def X(self, d):
         return self.R[self.rows[d, :self.tlen[d]]]
 
+    def P64(self, d):
+        """The float64 matrix of date d: the dense batches' own P + p_diag I, else the rounding of window_P."""
+        if hasattr(self, "P"):
+            return self.P[d] + self.opt[d].p_diag * np.eye(self.n)
+        return window_P(self.X(d), None if self.mu is None else self.mu[d], self.psw(d), self.opt[d].p_diag).astype(np.float64)
 
-def family_windows(fam, n=N, t=T):
-    """The batch without its optima: panel, windows, box and rows (everything but q and p_diag)."""
-    sizes, nplain = family_sizes(fam)
+
+R_GROUPS = 40              # family R: disjoint groups (variable i in group i mod 40) next to the budget row
+
+
+def family_windows(fam, n=N, t=T, sizes=None, nplain=0):
+    """The batch without its optima: panel, windows, box and rows (everything but q and p_diag).
+    ``sizes``: the free-set size of every date in place of family_sizes(fam), the first ``nplain``
+    dates without a ridge."""
+    if sizes is None:
+        sizes, nplain = family_sizes(fam)
+    sizes = np.asarray(sizes)
     D = len(sizes)
     ends = np.arange(t + 5, t + 5 + D)
     _, R, _, sec = factor_panel(int(ends.max()) + 1, n, n_sectors=10)
@@ -322,17 +409,28 @@ def family_windows(fam, n=N, t=T):
         lb = np.full(n, -1.0)
     elif fam.startswith("C"):
         C = np.vstack([C] + [(sec == g).astype(float)[None, :] for g in range(10)])
+    elif fam.startswith("R"):
+        sec = np.arange(n) % R_GROUPS
+        C = np.vstack([C] + [(sec == g).astype(float)[None, :] for g in range(R_GROUPS)])
+    elif fam == "N":     # box only: no general row at all
+        C, lg, ug = np.zeros((0, n)), np.zeros(0), np.zeros(0)
+    elif fam == "U":     # no box: every variable free, budget
+        lb, ub = np.full(n, -np.inf), np.full(n, np.inf)
     b = Batch(fam=fam, n=n, rows=rows, tlen=tlen, R=R, centred=fam != "W", p_scale=2.0, lb=lb, ub=ub, C=C,
               lg=lg, ug=ug, sizes=sizes, nplain=nplain)
     b.sec = sec
     return b
 
 
-def family(fam, mu=None, seed=SEED) -> Batch:
+def family(fam, mu=None, seed=SEED, n=N, t=T, sizes=None, ridge=None, nplain=0, dense=False) -> Batch:
     """The batch of a family with its optima.  ``mu`` (D, n): the float64 window means the kernels
-    are given (read back from the device); default: numpy's means of the same windows."""
-    b = family_windows(fam)
+    are given (read back from the device); default: numpy's means of the same windows.  (n, t, sizes,
+    nplain): another shape (family_windows); ``ridge``: in place of RIDGE[family].  ``dense``: the
+    optima of P64 + p_diag I with P64 the float64 rounding of the window's P without its ridge, kept per
+    date in ``b.P`` -- the matrix the dense kernels are given, with p_scale = 1 and the ridge as p_diag."""
+    b = family_windows(fam, n, t, sizes, nplain)
     n, D = b.n, b.D
+    ngr = R_GROUPS if fam.startswith("R") else 10
     rng = np.random.default_rng([seed, sum(map(ord, fam))])
     if b.centred and mu is None:
         mu = np.stack([b.X(d).mean(0) for d in range(D)])
@@ -341,36 +439,42 @@ def family(fam, mu=None, seed=SEED) -> Batch:
     if b.nplain < D:
         md = [float(np.mean(np.diag(window_P(b.X(d), None if b.mu is None else b.mu[d], b.psw(d), 0.0))))
               for d in range(b.nplain, D)]
-        b.ridge = float(RIDGE[fam[0]] * np.mean(md))
-    if fam.startswith("C"):
+        b.ridge = float((RIDGE[fam[0]] if ridge is None else ridge) * np.mean(md))
+    if fam.startswith(("C", "R")):
         nact = int(fam[1:])
-        tot = rng.uniform(0.9, 1.1, 10)
+        tot = rng.uniform(0.9, 1.1, ngr)
         tot = tot / tot.sum()
-        tot[9] = 1.0 - tot[:9].sum()
-        active = np.zeros(10, dtype=bool)
-        active[rng.permutation(10)[:nact]] = True
-        b.lg = np.concatenate([[1.0], np.full(10, -np.inf)])
+        tot[ngr - 1] = 1.0 - tot[:ngr - 1].sum()
+        active = np.zeros(ngr, dtype=bool)
+        active[rng.permutation(ngr)[:nact]] = True
+        b.lg = np.concatenate([[1.0], np.full(ngr, -np.inf)])
         b.ug = np.concatenate([[1.0], np.where(active, tot, tot + 0.05)])
         b.active = active
     for d in range(D):
         k = int(b.sizes[d])
         pd = 0.0 if d < b.nplain else b.ridge
         P = window_P(b.X(d), None if b.mu is None else b.mu[d], b.psw(d), pd)
+        if dense:
+            b.P = getattr(b, "P", []) + [window_P(b.X(d), None if b.mu is None else b.mu[d], b.psw(d), 0.0).astype(np.float64)]
+            P = b.P[-1].astype(LD)
+            P[np.diag_indices_from(P)] += LD(pd)
         side = np.ones(n, dtype=np.int64)
         x0 = np.zeros(n)
         act = np.zeros(b.C.shape[0], dtype=bool)
-        if fam.startswith("C"):
+        if fam.startswith(("C", "R")):
             # the free variables dealt evenly over the sectors (a sector's total is shared by every date, so
             # its free weights scale with 1 / their number); x*_F normalised per sector
-            F = np.sort(np.concatenate([rng.permutation(np.flatnonzero(b.sec == g))[:k // 10 + (g < k % 10)]
-                                        for g in range(10)]))
+            F = np.sort(np.concatenate([rng.permutation(np.flatnonzero(b.sec == g))[:k // ngr + (g < k % ngr)]
+                                        for g in range(ngr)]))
             assert len(F) == k
             side[F] = 0
             r = rng.uniform(0.5, 1.5, n)
-            for g in range(10):
+            for g in range(ngr):
                 m = (b.sec == g) & (side == 0)
                 x0[m] = r[m] / r[m].sum() * b.ug[1 + g] if b.active[g] else r[m] / r[m].sum() * (b.ug[1 + g] - 0.05)
             act[1:] = b.active
+        elif k == 0:            # every weight at a bound, the budget met by those at ub (0.05: 20 of them; 1: one)
+            side[rng.permutation(n)[:int(round(1.0 / b.ub[0]))]] = 2
         else:
             F = np.sort(rng.permutation(n)[:k])
             side[F] = 0
@@ -382,8 +486,8 @@ def family(fam, mu=None, seed=SEED) -> Batch:
                 side[Bv] = 1 + (rng.uniform(size=len(Bv)) < 0.5)
             xB = np.where(side == 1, b.lb, np.where(side == 2, b.ub, 0.0)).sum()
             r = rng.uniform(0.5, 1.5, k)
-            x0[F] = r / r.sum() * (1.0 - xB)
-        norm_width = 1.0 / (4 * k)
+            x0[F] = r / (r.sum() + 1.0) if fam == "N" else r / r.sum() * (1.0 - xB)   # (N: no budget to meet)
+        norm_width = 1.0 / (4 * max(k, 1))
         b.opt.append(manufacture(P, b.lb, b.ub, b.C, b.lg, b.ug, x0, side, act, rng, p_diag=pd,
                                  norm_width=norm_width))
     return b
@@ -392,7 +496,161 @@ def family(fam, mu=None, seed=SEED) -> Batch:
 FAMILIES = ("A", "B", "C1", "C7", "C8", "W")
 
 
+# ----------------------------------------------------------------------------------------
+# a synthetic start point for the per-date kernels, and the rules that classify it
+# ----------------------------------------------------------------------------------------
+
+
+def rule_start_box(z, y, x, lb, ub):
+    """polish_rules.h start_box (fix_thr = -inf), restated: 0 free, 1 at lb, 2 at ub, per variable."""
+    f = np.zeros(len(x), dtype=np.int64)
+    lo = np.isfinite(lb) & (z - lb < -y)
+    up = np.isfinite(ub) & (ub - z < y) & ~lo
+    f[lo], f[up] = 1, 2
+    f[lb == ub] = 1
+    return f
+
+
+def rule_start_row(z, y, lg, ug):
+    """polish_rules.h start_row, restated: 0 inactive, 1 at lg, 2 at ug (equality rows: 2), per row."""
+    a = np.zeros(len(lg), dtype=np.int64)
+    lo = np.isfinite(lg) & (z - lg < -y)
+    up = np.isfinite(ug) & (ug - z < y) & ~lo
+    a[lo], a[up] = 1, 2
+    a[lg == ug] = 2
+    return a
+
+
+def start_state(b: Batch, d: int, rel=1e-7, flip=None, seed=5):
+    """The point (x, z, y) the per-date kernels classify from, z and y over the rows [general; box]:
+    x = x* with x_F moved by ``rel`` x max |x*| (seeded), z_box = x clipped to the box, y_box = z* (zero
+    on F), z_rows = C x, y_rows = lambda* (1 + rel u).  start_box then returns ``side`` and start_row the
+    active rows exactly (tests/test_manufactured.py).  ``flip``: one variable per date starts wrongly
+    classified -- "fix": a free variable starts fixed at lb (z = lb, y = -tiny); "free": a variable at a
+    bound starts free (y = 0).  Returns (x, z, y, i): i the flipped variable or -1."""
+    o = b.opt[d]
+    rng = np.random.default_rng([seed, d])
+    mg = b.C.shape[0]
+    x = o.x.astype(np.float64)
+    x[o.F] += rel * float(np.abs(o.x).max()) * rng.uniform(-1, 1, o.k)
+    zb = np.clip(x, b.lb, b.ub)
+    yb = o.z.astype(np.float64)
+    yr = o.lam.astype(np.float64) * (1.0 + rel * rng.uniform(-1, 1, mg))
+    i = -1
+    if flip == "fix":
+        i = int(o.F[rng.integers(o.k)])
+        zb[i], yb[i] = b.lb[i], -np.finfo(np.float64).tiny
+    elif flip == "free":
+        B = np.flatnonzero(o.side != 0)
+        i = int(B[rng.integers(len(B))])
+        yb[i] = 0.0
+    elif flip is not None:
+        raise ValueError(flip)
+    return x, np.concatenate([b.C @ x, zb]), np.concatenate([yr, yb]), i
+
+
 def in_tight_bar(fam, o: Optimum) -> bool:
     """The date's last round runs on a solver reduced_kkt_f64 models (register tile, LDS solve, k_pg_big:
     k <= PG_KBIG = 256 free variables and at most 8 active rows; family W takes the wide rounds)."""
     return fam != "W" and o.k <= 256 and int(o.act.sum()) <= 8
+
+
+# ----------------------------------------------------------------------------------------
+# the batches of tests/test_polish_per_date_gpu.py: name -> family() arguments, and what the test runs
+# them as (mode "compact" / "woodbury" / "dense": the yardstick that models the batch; ldk: the
+# scratch of the launch).  ridge (x mean diag P): chosen on the CPU so that 10 d_model <= 1e-9 from the
+# 1e-7 start (tests/test_manufactured.py; the d_model reached is in that module's docstring)
+# ----------------------------------------------------------------------------------------
+
+def _pd(fam, sizes, mode="compact", ldk=256, n=N, t=T, ridge=4.0, **kw):
+    return dict(fam=fam, sizes=tuple(sizes), mode=mode, ldk=ldk, n=n, t=t, ridge=ridge, **kw)
+
+
+PER_DATE = {
+    # compact mode: form_pff_small<1>, <2>, form_pff and their tile edges
+    "cA": _pd("A", (2, 63, 64, 65, 127, 128, 129, 192, 193, 256)),
+    "cT20": _pd("A", (100, 100), t=20), "cT32": _pd("A", (100, 100), t=32),
+    "cT33": _pd("A", (100, 100), t=33), "cT65": _pd("A", (100, 100), t=65),
+    "cB": _pd("B", (30, 100, 129, 200)),
+    "cW": _pd("W", (64, 100, 200, 256)),
+    "cK0": _pd("B", (0, 0)),
+    "cR16": _pd("R16", (120, 120)), "cR32": _pd("R32", (120, 120)),
+    "cN": _pd("N", (1, 64, 130, 256)),
+    "cBig": _pd("A", (64, 200), n=1027, t=60),
+    # Woodbury mode (k > ldk >= 64 ceil(T / 64)); sizes n - nfix, nfix = 0, 1, 7, 8, 9, 128, 129
+    "wA": _pd("A", (300, 299, 293, 292, 291, 172, 171), "woodbury", 128),
+    "wW": _pd("W", (300, 299, 293, 292, 291, 172, 171), "woodbury", 128),
+    "wT64": _pd("A", (300, 292, 200, 65), "woodbury", 64, t=64),
+    "wT60": _pd("A", (300, 292, 200, 65), "woodbury", 64, t=60),
+    "wT65": _pd("A", (300, 292, 129), "woodbury", 128, t=65),
+    "wN": _pd("N", (300, 290, 150), "woodbury", 64, t=60),
+    "wC8": _pd("C8", (150, 200), "woodbury", 64, t=60),
+    # the dense kernel
+    "dA": _pd("A", (0, 64, 65, 200, 301), "dense", n=301, dense=True),
+    "dN": _pd("N", (1, 65), "dense", n=301, dense=True),
+    "dA1024": _pd("A", (64, 200, 1024), "dense", n=1024, dense=True),
+    "dC8": _pd("C8", (64, 200), "dense", n=301, dense=True),
+    "dU": _pd("U", (301, 301), "dense", n=301, dense=True),
+    # multi-round dates (start_state flip) and the engine leg
+    "fA": _pd("A", (40, 64, 100, 129, 200, 256), flip=True),
+    "fW": _pd("A", (299, 292, 250, 200, 172, 150), "woodbury", 128, flip=True),
+    # overflow: free sets beyond a scratch of 64 that is too small for the T = 120 capacitance, and the relaunch
+    "oA": _pd("A", (30, 65, 200, 64, 129), ldk=64),
+    "eC": _pd("A", (20, 40, 64), ldk=64, t=60),
+    "eW": _pd("A", (100, 200), "woodbury", 64, t=60),
+}
+
+
+def per_date(name, mu=None) -> Batch:
+    c = PER_DATE[name]
+    b = family(c["fam"], mu=mu, n=c["n"], t=c["t"], sizes=c["sizes"], ridge=c["ridge"], dense=c.get("dense", False))
+    b.name, b.mode, b.ldk = name, c["mode"], c["ldk"]
+    return b
+
+
+def full_rows(b: Batch):
+    """(C, l, u) over the rows [general; box] with the +-1e30 infinities of tests/engine_model.py."""
+    C = np.vstack([b.C, np.eye(b.n)])
+    l = np.concatenate([np.where(np.isfinite(b.lg), b.lg, -1e30), np.where(np.isfinite(b.lb), b.lb, -1e30)])
+    u = np.concatenate([np.where(np.isfinite(b.ug), b.ug, 1e30), np.where(np.isfinite(b.ub), b.ub, 1e30)])
+    return C, l, u
+
+
+FLIP_TRIES = 8
+
+
+def flip_start(b: Batch, d: int, delta=1e-9, dual_tol=1e-9, rounds=8, refine=1):
+    """A start_state of date d with one variable wrongly classified ("fix" on even dates, "free" on odd
+    ones) from which the engine's algorithm restated in numpy (tests/engine_model.py polish) ends at
+    (F, active rows) in more than one and at most ``rounds`` rounds: (x, z, y, i, kind, model rounds).
+    A draw that fails either condition is replaced by the next seed; None when FLIP_TRIES draws failed."""
+    from tests.engine_model import polish
+    o = b.opt[d]
+    P = window_P(b.X(d), None if b.mu is None else b.mu[d], b.psw(d), o.p_diag).astype(np.float64)
+    C, l, u = full_rows(b)
+    sc = problem_scale(b.X(d), None if b.mu is None else b.mu[d], b.psw(d), o.p_diag, o.q)
+    kind = "fix" if d % 2 == 0 else "free"
+    for seed in range(100, 100 + FLIP_TRIES):
+        x, z, y, i = start_state(b, d, flip=kind, seed=seed)
+        xm, lam, zb, nr, ok = polish(P, o.q, C, l, u, x, y, z, delta=delta * sc, rounds=rounds, refine=refine,
+                                     dual_tol=dual_tol * sc)
+        free = np.flatnonzero((xm > b.lb) & (xm < b.ub))
+        if ok and 1 < nr <= rounds and np.array_equal(free, o.F) and np.array_equal(np.flatnonzero(zb == 0.0), o.F) \
+                and np.abs(xm - o.x).max() <= 1e-9 * np.abs(o.x).max():
+            return x, z, y, i, kind, nr
+    return None
+
+
+def per_date_model(b: Batch, d: int, x0, lam0, delta_rel, refine):
+    """The yardstick that models the batch's mode, from (x0, lam0): ((x, lam, z_box, steps), problem scale)."""
+    o = b.opt[d]
+    if b.mode == "dense":
+        P = b.P64(d)
+        sc = max(float(np.abs(o.q).max()), float(np.abs(np.diag(P)).max()))
+        return reduced_kkt_f64(None, None, 1.0, 0.0, o.q, b.C, b.lg, b.ug, b.lb, b.ub, o.side, o.act, x0, lam0,
+                               delta_rel * sc, refine, stop=STOP_REL * sc, P=P), sc
+    X, mu = b.X(d), None if b.mu is None else b.mu[d]
+    sc = problem_scale(X, mu, b.psw(d), o.p_diag, o.q)
+    f = reduced_kkt_woodbury_f64 if b.mode == "woodbury" else reduced_kkt_f64
+    return f(X, mu, b.psw(d), o.p_diag, o.q, b.C, b.lg, b.ug, b.lb, b.ub, o.side, o.act, x0, lam0, delta_rel * sc,
+             refine, stop=STOP_REL * sc), sc

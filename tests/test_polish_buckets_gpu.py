@@ -42,8 +42,9 @@ mode with refine_retry steps, the register-tile, LDS and k_pg_big solvers, per d
 with d_model the same distance for the float64 yardstick manufactured.reduced_kkt_f64 started
 from the kernel's own ADMM point (read back from a run without polish), and 10 d_model <= 1e-9
 asserted (tests/test_manufactured.py bounds d_model by the reference alone, from any starting
-point).  The wide rounds and the per-date kernel keep (b): their algebra (a group capacitance
-at delta_wide; a Woodbury form) has no float64 model here yet.
+point).  The wide rounds keep (b): their algebra (a group capacitance at delta_wide) has no
+float64 model here yet.  The per-date kernel keeps (b) in this file and is held to (c), in its
+compact and its Woodbury mode, by tests/test_polish_per_date_gpu.py.
 
 Two properties of the kernels' algorithm had to be restated in the yardstick and in the
 problems, neither fitted to a measured number:
