@@ -854,6 +854,44 @@ int pq_rank_cov_batched(const double* panel, int64_t ldp, int32_t n, const int32
                         int32_t stages, void* scratch, int64_t ldr, double* diag, int64_t ldd, double* out,
                         int32_t ld, int64_t out_stride, int32_t* status, void* stream);
 
+/* Exponentially weighted covariance (RiskMetrics 1996) of every date, with NumPy's and pandas'
+ * definition (np.cov(aweights=w), ewm(adjust=True).cov(bias=False)).  X is date b's T x n window,
+ * oldest row first, read exactly as pq_cov_batched reads it; wage (tmax + 1 doubles, built by the
+ * caller; wage[k] is the weight of a row of age k, the newest row has age 0) gives
+ *   w_j = wage[T - 1 - j],  W1 = sum w,  W2 = sum w^2,  m = sum w_j x_j / W1,
+ *   out = sum_j w_j (x_j - m)(x_j - m)' / (W1 - W2 / W1).
+ * A window shorter than tmax takes its ages from its own end.  The kernels read the table and form
+ * no power themselves; wsqrt (tmax + 1 doubles of scratch) receives its square roots, which scale
+ * both operands of the matrix products.  A first kernel writes m into mean (batch x mean_stride, zeros in [n, ld)),
+ * (W1, W1 - W2 / W1) into wsum (batch x 2) and the status; then
+ *   gstart == NULL: one workgroup per lower 64 x 64 tile and date forms the weighted SYRK on the
+ *     FP64 matrix cores and writes the tile and its mirror;
+ *   gstart, shift: a slide plan as for pq_cov_slide_batched (ngroups + 1 date offsets; shift[d] the
+ *     rows by which date d's window moved against date d - 1's, both of one length).  The first
+ *     date of a group is formed as above, shifted by its own mean c; a later one by the recursion
+ *     A <- wage[s] A + entering rows - leaving rows (2 s n^2 flops) and written as
+ *     (A - W1 (m - c)(m - c)') / (W1 - W2 / W1).  wage must then be multiplicative up to rounding
+ *     (wage[j + k] = wage[j] wage[k]), as decay^k and 0.5^(k / halflife) are.
+ * out is batch x ld x ld (date stride out_stride >= ld^2), ld a multiple of 64 >= n: the whole
+ * block of a date is written, [0, n) x [0, n) with the result, symmetric bit for bit, the padding
+ * with zeros.  status[b]: PQ_EWMA_OK, or PQ_EWMA_BAD_INPUT -- T < 2, a non-finite value in the
+ * window, W1 - W2 / W1 not > 0 (a decay so fast that only the newest row has weight) --, for which
+ * the date's n x n block is NaN; inside a slide group the date after a bad one starts the
+ * recursion afresh, so nothing faults and no date affects another.  No atomics: the same input
+ * gives the same bits.
+ * 1 <= tmax <= PQ_EWMA_TMAX (the bound of pq_gerber_cov_batched: the kernels themselves have no
+ * limit, the bound keeps one window contract for the per-date estimators), n >= 1, ldp >= n,
+ * mean_stride >= ld.  The call does not synchronise; only host-checkable arguments return an
+ * error, and then nothing is launched. */
+#define PQ_EWMA_OK 0
+#define PQ_EWMA_BAD_INPUT 1
+#define PQ_EWMA_TMAX 1024
+int pq_ewma_cov_batched(const double* panel, int64_t ldp, int32_t n, const int32_t* rows, const int32_t* tlen,
+                        int32_t tmax, int32_t batch, const double* wage, double* wsqrt, double* mean,
+                        int64_t mean_stride, double* wsum, double* out, int32_t ld, int64_t out_stride,
+                        int32_t* status, const int32_t* gstart, int32_t ngroups, const int32_t* shift,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,10 @@ PQ_RANK_COV, PQ_RANK_CORR, PQ_RANK_COUNTS = range(3)
 PQ_RANK_RANKS, PQ_RANK_FINISH = 1, 2
 PQ_RANK_TMAX = 512
 
+# pq_ewma_cov_batched: per-date status and the longest window (the bound of the Gerber estimator)
+PQ_EWMA_OK, PQ_EWMA_BAD_INPUT = range(2)
+PQ_EWMA_TMAX = PQ_GERBER_TMAX
+
 PQ_PG_RECORD = 384                  # doubles per problem of the grouped polish record
 PQ_PG_PASS_SCRATCH = 123537          # doubles per slide group of the split polish window passes
 PQ_PG_PENDING, PQ_PG_DONE, PQ_PG_FALLBACK, PQ_PG_SKIP = range(4)
@@ -278,6 +282,8 @@ _EXPORTS = {
                                c_int64, c_dp, c_dp], c_int32),
     "pq_rank_cov_batched": ([c_dp, c_int64, c_int32, c_dp, c_dp, c_int32, c_int32, c_dp, c_int64, c_int32, c_int32,
                              c_int32, c_dp, c_int64, c_dp, c_int64, c_dp, c_int32, c_int64, c_dp, c_dp], c_int32),
+    "pq_ewma_cov_batched": ([c_dp, c_int64, c_int32, c_dp, c_dp, c_int32, c_int32, c_dp, c_dp, c_dp, c_int64, c_dp,
+                             c_dp, c_int32, c_int64, c_dp, c_dp, c_int32, c_dp, c_dp], c_int32),
 }
 
 _lib = None

@@ -19,7 +19,9 @@ gerber1 / gerber2): co-movement counts of the raw returns beyond ``threshold`` w
 deviations in place of the second moments (engine.gerber_cov; spec ``threshold`` 0.5 and
 ``variant`` 2 by default), and 'spearman' / 'kendall' are the rank correlations -- Spearman's rho
 and Kendall's tau-b of the window's columns, with mid-ranks for ties -- scaled by the window's
-standard deviations (engine.rank_cov).  ``estimate_batch`` is the batched backtest entry: all
+standard deviations (engine.rank_cov), and 'ewma' is the exponentially weighted covariance
+(RiskMetrics 1996; np.cov(aweights=), pandas' ewm().cov()) with spec ``halflife`` or ``decay``
+(engine.ewma_cov).  ``estimate_batch`` is the batched backtest entry: all
 rebalance dates of a device-resident panel at once, results left on the device.
 """
 from __future__ import annotations
@@ -55,7 +57,7 @@ SHRINKAGE_METHODS = ("ledoit_wolf", "oas")
 RANK_METHODS = ("spearman", "kendall")
 # methods estimated per date from the date's own window, as a dense matrix only: no window form
 # that dates could share (estimate_batch_lr serves them with materialise=True only)
-DENSE_ONLY_METHODS = ("gerber",) + RANK_METHODS
+DENSE_ONLY_METHODS = ("gerber",) + RANK_METHODS + ("ewma",)
 
 
 class Covariance:
@@ -81,12 +83,21 @@ class Covariance:
     complete windows.  Both are positive semi-definite by construction, and Kendall's tau-b is
     positive definite on typical windows with more assets than rows, where Spearman's rho (like the
     sample covariance) is singular.  The ranks belong to each date's own window, so
-    ``estimate_batch_lr`` serves them with ``materialise=True`` only."""
+    ``estimate_batch_lr`` serves them with ``materialise=True`` only.
+
+    method 'ewma' (spec ``halflife`` in rows, > 0, inf allowed, or ``decay`` in (0, 1]; both raise
+    ValueError, neither means decay = 0.94, the RiskMetrics daily value; a bad value raises
+    ValueError before the device is touched): the dense estimate of engine.ewma_cov, for complete
+    windows, positive semi-definite by construction.  The weight of a row depends on its age in
+    each date's window, so ``estimate_batch_lr`` serves it with ``materialise=True`` only; with a
+    ``plan`` the dates of a slide group are formed by the decaying recursion."""
 
     def __init__(self, spec: CovarianceSpecification = None, *args, **kwargs):
         self.spec = CovarianceSpecification(*args, **kwargs) if spec is None else spec
         if self.spec["method"] == "gerber":
             self.gerber_spec   # a bad threshold or variant is refused here, before any device work
+        if self.spec["method"] == "ewma":
+            self.ewma_spec     # likewise a bad halflife or decay
         self.shrinkage_ = None
         self.shrinkage_batch_ = None
         self.n_factors_ = None
@@ -113,6 +124,8 @@ class Covariance:
             covmat = cov_gerber(X, *self.gerber_spec)
         elif method in RANK_METHODS:
             covmat = _cov_rank(X, method)
+        elif method == "ewma":
+            covmat = cov_ewma(X, *self.ewma_spec)
         else:
             raise NotImplementedError("This method is not implemented yet")
         if self.spec.get("check_positive_definite") and not isPD(covmat):
@@ -133,6 +146,12 @@ class Covariance:
         ValueError for a threshold outside (0, 1] or a variant other than 1 or 2."""
         th, var = self.spec.get("threshold"), self.spec.get("variant")
         return _gerber_check(0.5 if th is None else th, 2 if var is None else var)
+
+    @property
+    def ewma_spec(self):
+        """(halflife, decay) of method 'ewma', one of them None (decay 0.94 where the spec gives
+        neither); ValueError for both given or a value outside its range."""
+        return _ewma_check(self.spec.get("halflife"), self.spec.get("decay"))
 
     def window_form_pca(self, panel, rows, tlen):
         """method 'pca' for every window of the device row table: engine.pca_window_form's factor
@@ -195,6 +214,19 @@ class Covariance:
                 return None, None, None, None
             from . import engine
             S, _, _ = engine.rank_cov(panel, rows, tlen, kind=method, out=out)   # (it zeroes the padding)
+            return S, torch.zeros(int(rows.shape[0]), dtype=torch.float64, device=S.device), None, None
+        if method == "ewma":
+            halflife, decay = self.ewma_spec
+            if not materialise:
+                raise NotImplementedError("the 'ewma' covariance has no window form: the weight of a row is "
+                                          "its age in each date's own window and so differs from date to date, "
+                                          "the dates of a slide group share no scaled row; estimate the dense "
+                                          "matrix (materialise=True)")
+            if panel.has_nan:   # complete windows only: the serial loop reports it
+                return None, None, None, None
+            from . import engine
+            S, _, _ = engine.ewma_cov(panel, rows, tlen, halflife=halflife, decay=decay, plan=plan,
+                                      out=out)   # (it zeroes the padding)
             return S, torch.zeros(int(rows.shape[0]), dtype=torch.float64, device=S.device), None, None
         if method not in ("pearson", "linear_shrinkage") + SHRINKAGE_METHODS:
             raise NotImplementedError("This method is not implemented yet")
@@ -388,6 +420,54 @@ def _cov_rank(X, kind):
     S, status, _ = engine.rank_cov(pan, rows, tlen, kind=kind)
     if int(status[0].item()) != _lib.PQ_RANK_OK:
         raise ValueError(f"the {kind} covariance: bad input (fewer than 2 rows, non-finite data or a constant column)")
+    S = S[0, :n, :n].cpu().numpy()
+    if isinstance(X, pd.DataFrame):
+        S = pd.DataFrame(S, index=X.columns, columns=X.columns)
+    return S
+
+
+EWMA_DEFAULT_DECAY = 0.94   # RiskMetrics' daily value
+
+
+def _ewma_check(halflife, decay):
+    """(halflife, decay) as floats, one of them None; neither given: decay = EWMA_DEFAULT_DECAY.
+    ValueError for both given, a halflife not > 0 (inf is allowed, NaN is not) or a decay outside
+    (0, 1] (host arithmetic only: a spec is refused before anything touches the device)."""
+    def real(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+    if halflife is not None and decay is not None:
+        raise ValueError("ewma: give halflife or decay, not both")
+    if halflife is not None:
+        if not real(halflife) or not float(halflife) > 0.0:
+            raise ValueError(f"ewma: halflife = {halflife!r} must be > 0 (rows; inf allowed)")
+        return float(halflife), None
+    if decay is None:
+        return None, EWMA_DEFAULT_DECAY
+    if not real(decay) or not 0.0 < float(decay) <= 1.0:
+        raise ValueError(f"ewma: decay = {decay!r} must lie in (0, 1]")
+    return None, float(decay)
+
+
+def cov_ewma(X, halflife=None, decay=None):
+    """Exponentially weighted covariance (RiskMetrics 1996) of one complete window, oldest row
+    first: engine.ewma_cov at batch 1 -- np.cov(X, rowvar=False, aweights=w) with
+    w = 0.5 ** (age / halflife) or decay ** age, the last block of
+    X.ewm(halflife=h).cov(bias=False).  ValueError for a bad spec, missing values or a bad-input
+    window."""
+    halflife, decay = _ewma_check(halflife, decay)
+    from . import _lib, engine
+    Xv = np.ascontiguousarray(X.to_numpy() if hasattr(X, "to_numpy") else X, dtype=np.float64)
+    if np.isnan(Xv).any():
+        raise ValueError("the ewma covariance needs complete windows")
+    T, n = Xv.shape
+    if not 1 <= T <= _lib.PQ_EWMA_TMAX:
+        raise ValueError(f"the ewma covariance: bad input ({T} rows, supported: 2..{_lib.PQ_EWMA_TMAX})")
+    pan = engine.Panel(Xv)
+    rows, tlen = pan.rows_to_device(np.arange(T, dtype=np.int32)[None], np.array([T], dtype=np.int32))
+    S, status, _ = engine.ewma_cov(pan, rows, tlen, halflife=halflife, decay=decay)
+    if int(status[0].item()) != _lib.PQ_EWMA_OK:
+        raise ValueError("the ewma covariance: bad input (fewer than 2 rows, non-finite data, or a decay so fast "
+                         "that only the newest row has weight)")
     S = S[0, :n, :n].cpu().numpy()
     if isinstance(X, pd.DataFrame):
         S = pd.DataFrame(S, index=X.columns, columns=X.columns)

@@ -2213,6 +2213,64 @@ def rank_cov(panel: "Panel", rows, tlen, kind: str = "spearman", output: str = "
     return out, status, diag
 
 
+def ewma_age_weights(tmax: int, halflife=None, decay=None) -> np.ndarray:
+    """The age table of the exponentially weighted covariance, ``tmax + 1`` doubles built with NumPy
+    on the host (and only here, so that the kernels and a host model use the same bits):
+    wage[k] = 0.5 ** (k / halflife), or decay ** k; the spec is checked by covariance._ewma_check."""
+    from .covariance import _ewma_check
+    halflife, decay = _ewma_check(halflife, decay)
+    k = np.arange(int(tmax) + 1, dtype=np.float64)
+    if halflife is not None:
+        return np.power(0.5, k / halflife)
+    return np.power(decay, k)
+
+
+def ewma_cov(panel: "Panel", rows, tlen, halflife=None, decay=None, plan: "SlidePlan | None" = None, out=None):
+    """The exponentially weighted covariance (RiskMetrics 1996) of every window
+    (pq_ewma_cov_batched), with NumPy's and pandas' definition: a row of age k (the newest row of
+    a window has age 0) weighs w = 0.5 ** (k / halflife), or decay ** k,
+    Sigma = sum w (x - m)(x - m)' / (W1 - W2 / W1) with the weighted mean m, W1 = sum w and
+    W2 = sum w^2 -- np.cov(aweights=w), the last block of ewm(adjust=True).cov(bias=False).  One of
+    ``halflife`` (rows, > 0, inf allowed) and ``decay`` (0 < decay <= 1) may be given, neither means
+    decay = 0.94; halflife = inf or decay = 1 is the ddof = 1 sample covariance.  ``rows`` /
+    ``tlen``: the device row table, at most _lib.PQ_EWMA_TMAX rows per window.  ``plan``: a SlidePlan
+    of the same table; overlapping windows are then formed by the decaying rank-2s recursion
+    instead of a weighted SYRK per date (the same estimate to rounding).  ``out``: a (B, ld, ld)
+    buffer, ld = round_up(n, 64): [0, n) x [0, n) of every date carries the result, symmetric bit
+    for bit, and the padding is set to zero (None: a buffer is allocated).  Returns (S [B, ld, ld],
+    status [B] int32: _lib.PQ_EWMA_*, mean [B, ld] float64: the weighted means), on the device; a
+    PQ_EWMA_BAD_INPUT date (fewer than 2 rows, a non-finite value, a decay so fast that
+    W1 - W2 / W1 is not positive) has a NaN block and affects no other date.  ValueError for a bad
+    spec, a wrong ``out`` or a window length outside 1.._lib.PQ_EWMA_TMAX, before anything runs.
+    Does not synchronise."""
+    B, tmax = int(rows.shape[0]), int(rows.shape[1])
+    wage = ewma_age_weights(tmax, halflife, decay)
+    lib = _lib.load()
+    n, dev = panel.n, panel.device
+    ld = round_up(n, 64)
+    if not 1 <= tmax <= _lib.PQ_EWMA_TMAX:
+        raise ValueError(f"ewma_cov: windows of up to {tmax} rows (supported: 1..{_lib.PQ_EWMA_TMAX})")
+    if out is None:
+        out = torch.empty((B, ld, ld), dtype=F64, device=dev)
+    elif tuple(out.shape) != (B, ld, ld) or out.dtype != F64 or not out.is_contiguous():
+        raise ValueError(f"ewma_cov: out must be a contiguous float64 ({B}, {ld}, {ld}) tensor")
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    mean = torch.empty((B, ld), dtype=F64, device=dev)
+    if B == 0:
+        return out, status, mean
+    rows = rows.contiguous()
+    wdev = torch.from_numpy(wage).to(dev)
+    wsqrt = torch.empty_like(wdev)   # scratch: the square roots of the table
+    wsum = torch.empty((B, 2), dtype=F64, device=dev)
+    slide = plan is not None
+    _lib.check(lib.pq_ewma_cov_batched(_ptr(panel.R), panel.R.stride(0), n, _ptr(rows), _ptr(tlen), tmax, B,
+                                       _ptr(wdev), _ptr(wsqrt), _ptr(mean), mean.stride(0), _ptr(wsum), _ptr(out), ld,
+                                       out.stride(0), _ptr(status), _ptr(plan.gstart) if slide else None,
+                                       plan.ngroups if slide else 0, _ptr(plan.shift) if slide else None,
+                                       _stream()), "pq_ewma_cov_batched")
+    return out, status, mean
+
+
 PCA_CHUNK_BYTES = 2 << 30   # Gram, eigenvector and work buffers of pca_window_form stay below this
 # the eigensolver of pca_window_form where the caller names none: on the 4749 window Grams of config 3
 # (252 x 252) rocSOLVER's eigh takes 432 ms, the block-Jacobi kernels 2994 ms (profiles/pca_cov_bench.log)

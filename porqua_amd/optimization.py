@@ -152,7 +152,10 @@ class MeanVariance(Optimization):
     window form --; variant 1 can be indefinite, so ``objective_batch`` returns None and the serial
     loop lets ``Covariance.estimate`` check and repair every date.  'spearman' and 'kendall' are
     positive semi-definite by construction and take the dense batched route in the same way
-    (covariance.DENSE_ONLY_METHODS names the methods without a window form)."""
+    (covariance.DENSE_ONLY_METHODS names the methods without a window form).  'ewma' is one of them,
+    positive semi-definite by construction too, and the only one whose estimator takes the stage's
+    slide plan: the consecutive windows of a daily backtest are formed by the decaying recursion of
+    engine.ewma_cov."""
 
     batch_handles_nan = True   # windows with gaps: pairwise covariance + skipna means, batched
 
@@ -180,9 +183,11 @@ class MeanVariance(Optimization):
             return None
         nan = stage.panel.has_nan   # missing values: pairwise covariance, dense P (no window form)
         lowrank = stage.prefer_lowrank and method != "duv" and not nan and not dense_only
+        # (the dense-only estimators read each date's own window; 'ewma' alone has a sliding form)
+        no_plan = nan or lowrank or (dense_only and method != "ewma")
         S, pdiag, mu_c, dg = self.covariance.estimate_batch_lr(
             stage.panel, stage.rows, stage.tlen, out=None if lowrank else stage.P_buffer(),
-            plan=None if (nan or lowrank or dense_only) else stage.slide_plan(), materialise=not lowrank,
+            plan=None if no_plan else stage.slide_plan(), materialise=not lowrank,
             groups=stage.group_plan() if lowrank else None)
         ra = float(self.params["risk_aversion"])
         B = stage.batch
@@ -611,6 +616,9 @@ def covariance_window_form(covariance, panel, rows, tlen, dg):
         delta, _ = engine.shrinkage_intensity(panel, rows, tlen, kind=method)
         covariance.shrinkage_batch_ = delta
         return (1.0 - delta) * a, delta * md
+    if method == "ewma":
+        raise NotImplementedError("the 'ewma' covariance has no window form Sigma = a Xc'Xc + c I: its rows carry "
+                                  "one weight each, which a scalar a per date cannot express")
     raise NotImplementedError("This method is not implemented yet")
 
 
@@ -633,7 +641,9 @@ class RiskParity(Optimization):
     ``n_factors_batch_`` / ``noise_variance_batch_``, and a date whose factor model is bad input
     (sigma2 NaN) is PQ_RP_BAD_INPUT.  'gerber' is not served (NotImplementedError): the kernel
     needs a window form, and the Gerber thresholds are per date, so no rows are shared; nor are
-    'spearman' and 'kendall' (NotImplementedError): the ranks belong to each date's own window.
+    'spearman' and 'kendall' (NotImplementedError): the ranks belong to each date's own window;
+    nor is 'ewma' (NotImplementedError): its rows carry one weight each, and the kernel's window
+    form has a single scalar a per date.
 
     ``risk_budget``: a dict or Series over the assets (None: equal budgets); an asset of the
     date's selection without an entry is an error, entries must be > 0, and the budgets are
@@ -765,7 +775,8 @@ class HierarchicalRiskParity(Optimization):
     alpha = 1 and c = sigma2 (a date whose factor model is bad input is PQ_HRP_BAD_INPUT); 'gerber':
     S the dense estimate of engine.gerber_cov per chunk of dates, alpha = 1 and c = 0 (a bad-input
     date arrives as NaN and is PQ_HRP_BAD_INPUT by the kernel's own check); 'spearman' / 'kendall':
-    the dense estimate of engine.rank_cov in the same way.
+    the dense estimate of engine.rank_cov in the same way; 'ewma': the dense estimate of
+    engine.ewma_cov (its direct kernel) in the same way.
     ``linkage``: 'single' (Lopez de Prado's choice, the default), 'complete',
     'average' or 'weighted', with SciPy's meaning; any other name raises NotImplementedError --
     'ward' too, though the kernel has it: engine.hrp_weights(method='ward') reaches it --, and
@@ -819,6 +830,13 @@ class HierarchicalRiskParity(Optimization):
 
             def dense(r, t, out):
                 return engine.rank_cov(panel, r, t, kind=kind, out=out)[0]
+            return engine.hrp_weights(panel, rows, tlen, alpha=1.0, c=0.0, scale=self.budget_scale(),
+                                      linkage=linkage, method=self.linkage, dense=dense)
+        if self.covariance.spec["method"] == "ewma":   # the dense exponentially weighted estimate
+            halflife, decay = self.covariance.ewma_spec
+
+            def dense(r, t, out):
+                return engine.ewma_cov(panel, r, t, halflife=halflife, decay=decay, out=out)[0]
             return engine.hrp_weights(panel, rows, tlen, alpha=1.0, c=0.0, scale=self.budget_scale(),
                                       linkage=linkage, method=self.linkage, dense=dense)
         mu = panel.window_means(rows, tlen)
